@@ -4,7 +4,8 @@
 # limit, stopping at the first crash / abort / time-out.
 set -u
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}   # where the logs and records go
+mkdir -p "$OUT"
 STEPS="tests smoke bench" bash scripts/gpu_check.sh || exit $?
-timeout -k 10 600 python bench.py --model hem > gpurun_out/bench_hem.log 2>&1; rc=$?; echo "bench hem rc=$rc"; [ $rc = 0 ] || exit $rc
-timeout -k 10 600 python bench.py --yuv420 --steps 16 --no-cpu-baseline > gpurun_out/bench_c4.log 2>&1; rc=$?; echo "bench c4 rc=$rc"; [ $rc = 0 ] || exit $rc
+timeout -k 10 600 python bench.py --full --model hem > $OUT/bench_hem.log 2>&1; rc=$?; echo "bench hem rc=$rc"; [ $rc = 0 ] || exit $rc
+timeout -k 10 600 python bench.py --full --yuv420 --steps 16 --no-cpu-baseline > $OUT/bench_c4.log 2>&1; rc=$?; echo "bench c4 rc=$rc"; [ $rc = 0 ] || exit $rc

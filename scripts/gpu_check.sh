@@ -5,28 +5,29 @@
 # carries on past plain test failures (exit 1) so the bench still reports.
 set -u
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}   # where the logs and records go
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 STEPS=${STEPS:-tests bench prof}
 fatal() { case "$1" in 124|134|137|139) return 0;; *) return 1;; esac; }
 for s in $STEPS; do
   case $s in
     tests)
-      timeout -k 10 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider > gpurun_out/pytest_gpu.log 2>&1
-      rc=$?; echo "pytest gpu rc=$rc"; tail -5 gpurun_out/pytest_gpu.log
+      timeout -k 10 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1
+      rc=$?; echo "pytest gpu rc=$rc"; tail -5 $OUT/pytest_gpu.log
       fatal $rc && exit $rc ;;
     smoke)
-      timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
-      rc=$?; echo "smoke rc=$rc"; tail -3 gpurun_out/smoke.log
+      timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
+      rc=$?; echo "smoke rc=$rc"; tail -3 $OUT/smoke.log
       fatal $rc && exit $rc ;;
     bench)
-      timeout -k 10 900 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1
-      rc=$?; echo "bench rc=$rc"; tail -3 gpurun_out/bench.log
+      timeout -k 10 900 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1
+      rc=$?; echo "bench rc=$rc"; tail -3 $OUT/bench.log
       fatal $rc && exit $rc ;;
     prof)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv \
-        -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-roofline > gpurun_out/prof.log 2>&1
-      rc=$?; echo "prof rc=$rc"; tail -3 gpurun_out/prof.log
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv \
+        -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-roofline > $OUT/prof.log 2>&1
+      rc=$?; echo "prof rc=$rc"; tail -3 $OUT/prof.log
       fatal $rc && exit $rc ;;
   esac
 done
