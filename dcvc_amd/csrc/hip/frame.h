@@ -1,0 +1,93 @@
+// Helpers shared by the harness-side frame kernels (frame.hip, crossfmt.hip):
+// the NHWC frame view, the uint8 -> [0, 1] conversion, scipy's order-0 zoom
+// index map, the fixed-order squared-error reduction and the uint8
+// quantisation of the decoded-frame writers.
+#pragma once
+#include "common.h"
+
+namespace {
+
+struct FView {
+  float *p;
+  int H, W, cs, co;
+};
+
+__device__ __forceinline__ float u8f(uint8_t v) { return (float)v / 255.f; }
+
+// scipy.ndimage.zoom(uv, (1, 2, 2), order=0) as ycbcr420_to_444(order=0)
+// calls it (DCVC-DC/src/transforms/functional.py:61-72): output index i of an
+// axis of length 2n samples input index round(i * (n - 1) / (2n - 1)).  The
+// product i(n-1)/(2n-1) is never a half-integer (2i(n-1) is even, (2n-1)
+// odd) and lies at least 1/(2(2n-1)) from one, so the double evaluation
+// rounds exactly as scipy's does.
+__device__ __forceinline__ int zoom_src(int i, int n) {
+  if (n <= 1) return 0;
+  const double z = (double)(n - 1) / (double)(2 * n - 1);
+  return (int)floor((double)i * z + 0.5);
+}
+
+constexpr int SSE_BLOCK = 256;
+constexpr int SSE_MAX_BLOCKS = 1024;
+
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// Block sum of three doubles in a fixed order: wave shuffles, then the four
+// wave results in index order.  Thread 0 writes part[3 * blockIdx.x + c].
+__device__ void block_sum3(double a0, double a1, double a2, double *part) {
+  __shared__ double red[SSE_BLOCK / 64][3];
+  a0 = wave_sum(a0);
+  a1 = wave_sum(a1);
+  a2 = wave_sum(a2);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[wv][0] = a0;
+    red[wv][1] = a1;
+    red[wv][2] = a2;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double s = 0.0;
+    for (int i = 0; i < SSE_BLOCK / 64; ++i) s += red[i][threadIdx.x];
+    part[3 * blockIdx.x + threadIdx.x] = s;
+  }
+}
+
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+
+__device__ __forceinline__ uint8_t q255(float v) {
+  return (uint8_t)fminf(fmaxf(rintf(v * 255.f), 0.f), 255.f);  // np.clip(np.rint(v * 255), 0, 255)
+}
+
+// Fixed-order final reduction of the per-block partials: out[c] = sum_b part[3b + c].
+__global__ void __launch_bounds__(256) sse_final_kernel(const double *part, int nb, double *out) {
+  __shared__ double red[4][3];
+  double a[3] = {0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < nb; b += 256)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a[c] += part[3 * b + c];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) a[c] = wave_sum(a[c]);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) red[wv][c] = a[c];
+  __syncthreads();
+  if (threadIdx.x < 3) out[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) +
+                                          red[3][threadIdx.x];
+}
+
+inline bool frame_ok(const dcvc_tensor &t) {
+  return t.ptr && t.dtype == DCVC_F32 && t.C == 3 && t.H > 0 && t.W > 0 && t.coff >= 0 && t.coff + 3 <= t.cstride;
+}
+
+inline FView fv(const dcvc_tensor &t) { return FView{reinterpret_cast<float *>(t.ptr), t.H, t.W, t.cstride, t.coff}; }
+
+inline unsigned sse_blocks(int64_t n) {
+  const int64_t g = (n + SSE_BLOCK - 1) / SSE_BLOCK;
+  return (unsigned)(g < SSE_MAX_BLOCKS ? (g > 0 ? g : 1) : SSE_MAX_BLOCKS);
+}
+
+}  // namespace

@@ -11,6 +11,16 @@ distortion with ``dcvc_frame_sse``, which also performs
 sums stay on the device until the end of the sequence (one transfer), and the
 PSNR formulas are evaluated on the host exactly as the reference writes them.
 
+The source format and the codec format are independent (test_video.py:79-119,
+video_reader.py:33-42): a YUV420 file can feed an RGB model and a PNG folder a
+YUV420 model.  The readers always hand over their native uint8 planes;
+``FrameStage(src_format=...)`` converts on the GPU (crossfmt.hip:
+``ycbcr420_to_rgb(order=1)`` or ``rgb_to_ycbcr420`` + ``ycbcr420_to_444``,
+bit-equal to the reference's numpy / scipy values), keeps the converted fp32
+source planes on the device, and the distortion and MS-SSIM compare against
+those (``dcvc_frame_sse_f32``, ``dcvc_*_planes_f64_f32``).  The decoded-frame
+writers' cross cases are quantised on the GPU too (``dcvc_recon_to_u8_cross``).
+
 MS-SSIM: for YUV420 sources ``calc_ssim`` runs the reference's per-plane
 ``calc_msssim`` (src/utils/metrics.py:39-62) on the GPU in fp64 (``MsSsim``,
 msssim.hip), pinned to the reference's outputs.  RGB MS-SSIM is
@@ -33,8 +43,9 @@ from .stream_helper import get_padding_size
 class YUVReader:
     """Raw 8-bit YUV420 file reader (DCVC-DC/src/utils/video_reader.py:
     121-161).  ``read_one_frame`` returns uint8 ``(y (h, w), uv (2, h/2,
-    w/2))``, or ``(None, None)`` at the end of the file; the reference's
-    float conversion (x / 255) happens on the GPU."""
+    w/2))``, or ``(None, None)`` at the end of the file, whatever
+    ``dst_format`` the codec wants; the reference's float conversion (x / 255)
+    and, for an RGB codec, its ycbcr420_to_rgb happen on the GPU (FrameStage)."""
 
     def __init__(self, src_path, width, height, src_format="420", skip_frame=0):
         if src_format != "420":
@@ -59,8 +70,8 @@ class YUVReader:
         return y, uv
 
     def read_one_frame(self, dst_format="420"):
-        if dst_format != "420":
-            raise ValueError("YUVReader hands over 420 planes; RGB sources use PNGReader")
+        if dst_format not in ("420", "rgb"):
+            raise ValueError(f"unknown dst_format {dst_format!r}")
         if self.eof:
             return None, None
         r = self._read()
@@ -76,7 +87,8 @@ class YUVReader:
 
 class PNGReader:
     """Folder of im1.png / im00001.png frames (video_reader.py:44-80);
-    returns uint8 CHW RGB, or None at the end."""
+    returns uint8 CHW RGB, or None at the end, whatever ``dst_format`` the
+    codec wants (FrameStage converts for a YUV420 codec)."""
 
     def __init__(self, src_path, width, height, start_num=1):
         pngs = os.listdir(src_path)
@@ -92,8 +104,8 @@ class PNGReader:
 
     def read_one_frame(self, dst_format="rgb"):
         from PIL import Image
-        if dst_format != "rgb":
-            raise ValueError("PNGReader hands over RGB frames")
+        if dst_format not in ("rgb", "420"):
+            raise ValueError(f"unknown dst_format {dst_format!r}")
         if self.eof:
             return None
         p = os.path.join(self.src_path, f"im{str(self.current_frame_index).zfill(self.padding)}.png")
@@ -132,10 +144,31 @@ class ArrayReader:
 # ----------------------------------------------------------- device staging
 class FrameStage:
     """Device side of one sequence: uint8 source upload, padded NHWC codec
-    input, and the per-frame squared-error sums (frame_num x 3, fp64)."""
+    input, and the per-frame squared-error sums (frame_num x 3, fp64).
 
-    def __init__(self, h, w, align, yuv420, zero_pad, frame_num, device):
+    ``src_format`` ("rgb" | "420") is what the reader hands over; it defaults
+    to the codec's own format (``yuv420``).  When it differs, ``load`` converts
+    the frame on the GPU and keeps the converted fp32 source planes
+    (``src_f32``: (rgb 3 x h x w,) or (y, uv)) for ``distortion`` and MS-SSIM:
+    the frame the reference's reader would have returned."""
+
+    def __init__(self, h, w, align, yuv420, zero_pad, frame_num, device, src_format=None):
         self.h, self.w, self.yuv, self.zero_pad = h, w, yuv420, zero_pad
+        codec_format = "420" if yuv420 else "rgb"
+        src_format = codec_format if src_format is None else src_format
+        if src_format not in ("rgb", "420"):
+            raise ValueError(f"unknown src_format {src_format!r}")
+        self.src_yuv = src_format == "420"
+        self.cross = src_format != codec_format
+        self.src_f32 = None
+        if self.cross:
+            if zero_pad or h % 2 or w % 2:
+                raise ValueError("a converted source needs even sizes and replicate padding")
+            if yuv420:
+                self.src_f32 = (torch.empty((h, w), dtype=torch.float32, device=device),
+                                torch.empty((2, h // 2, w // 2), dtype=torch.float32, device=device))
+            else:
+                self.src_f32 = (torch.empty((3, h, w), dtype=torch.float32, device=device),)
         _, pr, _, pb = get_padding_size(h, w, align)
         self.H, self.W = h + pb, w + pr
         self.dev = device
@@ -145,15 +178,21 @@ class FrameStage:
 
     def upload(self, frame):
         """Host uint8 frame (CHW RGB, or (y, uv)) -> device tensors."""
-        if self.yuv:
+        if self.src_yuv:
             y, uv = frame
             return K.upload(y, self.dev, "frame_y"), K.upload(uv, self.dev, "frame_uv")
         return K.upload(frame, self.dev, "frame")
 
     def load(self, dframe):
         """Device uint8 frame -> padded NHWC fp32 codec input (test_video.py:
-        108-132: ycbcr420_to_444(order=0) for YUV, x / 255, F.pad)."""
-        if self.yuv:
+        108-132: ycbcr420_to_444(order=0) for YUV, x / 255, F.pad; for a source
+        of the other format, the reader's conversion first)."""
+        if self.cross and self.yuv:
+            K.rgb_to_yuv420_planes(dframe, self.h, self.w, *self.src_f32)
+            K.yuv420f_to_nhwc(self.src_f32[0], self.src_f32[1], self.h, self.w, self.x)
+        elif self.cross:
+            K.yuv420_to_rgb_nhwc(dframe[0], dframe[1], self.h, self.w, self.x, self.src_f32[0])
+        elif self.yuv:
             K.yuv420_to_nhwc(dframe[0], dframe[1], self.h, self.w, self.x)
         else:
             K.frame_to_nhwc(dframe, self.h, self.w, self.x, zero_pad=self.zero_pad)
@@ -164,7 +203,11 @@ class FrameStage:
         frame into row ``slot`` (test_video.py:169-195)."""
         from .dc.video_model import as_act
         r = as_act(recon)
-        if self.yuv:
+        if self.cross and self.yuv:
+            K.frame_sse_f32(r, self.src_f32[0], self.h, self.w, self.ws, self.sse[slot], uv_f32=self.src_f32[1])
+        elif self.cross:
+            K.frame_sse_f32(r, self.src_f32[0], self.h, self.w, self.ws, self.sse[slot])
+        elif self.yuv:
             K.frame_sse(r, dframe[0], self.h, self.w, self.ws, self.sse[slot], uv_u8=dframe[1])
         else:
             K.frame_sse(r, dframe, self.h, self.w, self.ws, self.sse[slot])
@@ -208,6 +251,14 @@ class MsSsim:
 
     def run(self, x_hat, y_u8, uv_u8, slot):
         K.yuv_planes_f64(x_hat, y_u8, uv_u8, self.h, self.w, self.src, self.rec)
+        self._levels(slot)
+
+    def run_f32(self, x_hat, y_f32, uv_f32, slot):
+        """``run`` against fp32 source planes (FrameStage.src_f32 of an RGB source)."""
+        K.yuv_planes_f64_f32(x_hat, y_f32, uv_f32, self.h, self.w, self.src, self.rec)
+        self._levels(slot)
+
+    def _levels(self, slot):
         for p, (off, ph, pw, L, bufs) in enumerate(self.planes):
             a, b, sh, sw = self.src[off:off + ph * pw], self.rec[off:off + ph * pw], ph, pw
             for k in range(L):
@@ -260,6 +311,14 @@ class MsSsimRGB:
 
     def run(self, x_hat, src_u8, slot):
         K.rgb_planes_f64(x_hat, src_u8, self.h, self.w, self.src, self.rec)
+        self._levels(slot)
+
+    def run_f32(self, x_hat, src_f32, slot):
+        """``run`` against a planar fp32 source (FrameStage.src_f32 of a YUV420 source)."""
+        K.rgb_planes_f64_f32(x_hat, src_f32, self.h, self.w, self.src, self.rec)
+        self._levels(slot)
+
+    def _levels(self, slot):
         n = self.h * self.w
         for c in range(3):
             a, b, sh, sw = self.src[c * n:(c + 1) * n], self.rec[c * n:(c + 1) * n], self.h, self.w
@@ -297,17 +356,17 @@ class ReconWriter:
     so file encoding overlaps the next frame.  kind: "png" | "yuv" | "hem_png";
     src_format "rgb" | "420" (what the codec's frames hold, dist_in_yuv420).
     The reference's cross cases (a 4:2:0 frame into PNGWriter, an RGB frame into
-    YUVWriter) convert on the host with its own formulas
-    (functional.py:16-58)."""
+    YUVWriter, functional.py:16-58) are converted and quantised on the GPU as
+    well (dcvc_recon_to_u8_cross) and take the same pinned-copy path."""
 
     def __init__(self, path, h, w, kind, src_format, device):
         from concurrent.futures import ThreadPoolExecutor
         os.makedirs(path, exist_ok=True)
         self.path, self.h, self.w, self.kind, self.fmt = path, h, w, kind, src_format
         self.yuv_out = kind == "yuv"
-        quant_yuv = src_format == "420"
-        self.quant_yuv = quant_yuv
-        self.n = h * w + 2 * (h // 2) * (w // 2) if quant_yuv else 3 * h * w
+        self.quant_yuv = src_format == "420"
+        self.cross = self.quant_yuv != self.yuv_out
+        self.n = h * w + 2 * (h // 2) * (w // 2) if self.yuv_out else 3 * h * w
         self.dev_buf = torch.empty(self.n, dtype=torch.uint8, device=device)
         self.pool = ThreadPoolExecutor(1)
         self.jobs = []
@@ -317,17 +376,10 @@ class ReconWriter:
     def write(self, recon, frame_idx):
         from .dc.video_model import as_act
         x = as_act(recon)
-        if (self.fmt == "rgb") == self.yuv_out:
-            # the cross cases: the float frame to the host, the reference's conversion there
-            f = x.t()[:self.h, :self.w].float().permute(2, 0, 1).cpu().numpy()
-            if self.yuv_out:
-                self.jobs.append(self.pool.submit(self._yuv_from_rgb, f))
-            else:
-                name = f"im{str(self.index).zfill(5)}.png"
-                self.index += 1
-                self.jobs.append(self.pool.submit(self._png_from_444, f, name))
-            return
-        K.recon_to_u8(x, self.h, self.w, self.quant_yuv, self.dev_buf)
+        if self.cross:
+            K.recon_to_u8_cross(x, self.h, self.w, not self.yuv_out, self.dev_buf)
+        else:
+            K.recon_to_u8(x, self.h, self.w, self.quant_yuv, self.dev_buf)
         host = torch.empty(self.n, dtype=torch.uint8, pin_memory=True)
         host.copy_(self.dev_buf, non_blocking=True)
         ev = torch.cuda.Event()
@@ -345,37 +397,6 @@ class ReconWriter:
             return
         from PIL import Image
         Image.fromarray(a.reshape(h, w, 3)).save(os.path.join(self.path, name))
-
-    def _png_from_444(self, yuv, name):
-        # 4:2:0 frame into PNGWriter: ycbcr444_to_420 (y_rec, uv_rec as test_video.py:170-171 forms them),
-        # then ycbcr420_to_rgb(order=1) and the PNG quantisation (functional.py:42-58, video_writer.py:34-45)
-        import scipy.ndimage
-        from PIL import Image
-        h, w = self.h, self.w
-        y = np.clip(yuv[0:1], 0.0, 1.0)
-        u = np.mean(np.reshape(yuv[1:2], (1, h // 2, 2, w // 2, 2)), axis=(-1, -3))
-        v = np.mean(np.reshape(yuv[2:3], (1, h // 2, 2, w // 2, 2)), axis=(-1, -3))
-        uv = scipy.ndimage.zoom(np.clip(np.concatenate((u, v), axis=0), 0.0, 1.0), (1, 2, 2), order=1)
-        kr, kg, kb = 0.2126, 0.7152, 0.0722
-        r = y + (2 - 2 * kr) * (uv[1:2] - 0.5)
-        b = y + (2 - 2 * kb) * (uv[0:1] - 0.5)
-        g = (y - kr * r - kb * b) / kg
-        rgb = np.clip(np.concatenate((r, g, b), 0), 0.0, 1.0).transpose(1, 2, 0)
-        Image.fromarray(np.clip(np.rint(rgb * 255), 0, 255).astype(np.uint8)).save(os.path.join(self.path, name))
-
-    def _yuv_from_rgb(self, rgb):
-        r, g, b = np.split(rgb, 3, axis=0)
-        kr, kg, kb = 0.2126, 0.7152, 0.0722
-        y = kr * r + kg * g + kb * b
-        cb = 0.5 * (b - y) / (1 - kb) + 0.5
-        cr = 0.5 * (r - y) / (1 - kr) + 0.5
-        h, w = self.h, self.w
-        cb = np.mean(np.reshape(cb, (1, h // 2, 2, w // 2, 2)), axis=(-1, -3))
-        cr = np.mean(np.reshape(cr, (1, h // 2, 2, w // 2, 2)), axis=(-1, -3))
-        uv = np.clip(np.concatenate((cb, cr), axis=0), 0.0, 1.0)
-        y = np.clip(y, 0.0, 1.0)
-        self.file.write(np.clip(np.rint(y * 255), 0, 255).astype(np.uint8).tobytes())
-        self.file.write(np.clip(np.rint(uv * 255), 0, 255).astype(np.uint8).tobytes())
 
     def close(self):
         """Drain the writer thread and close out.yuv (idempotent)."""
@@ -503,22 +524,26 @@ def run_test(p_frame_net, i_frame_net, args):
     src_type 'png' | 'yuv420', src_path, src_width, src_height,
     dist_in_yuv420, q_in_ckpt, i_frame_q_index, verbose, calc_ssim) plus an
     optional ``src_reader`` (an ArrayReader) in place of a file source.
-    YUV420 sources are coded as YCbCr 4:4:4 (``dist_in_yuv420``), as the
-    reference's yuv420 checkpoints expect."""
+    ``dist_in_yuv420`` selects the codec's format (YCbCr 4:4:4 input, as the
+    reference's yuv420 checkpoints expect, against RGB) and ``src_type`` the
+    source's, independently; a source of the other format is converted on the
+    GPU as the reference's readers convert it (FrameStage)."""
     frame_num, gop_size = args["frame_num"], args["gop_size"]
     write_stream = bool(args.get("write_stream", False))
     verbose = args.get("verbose", 0)
     yuv = bool(args.get("dist_in_yuv420", False))
-    if yuv and args.get("src_type", "yuv420") != "yuv420" and "src_reader" not in args:
-        raise ValueError("dist_in_yuv420 needs a yuv420 source")
+    codec_fmt = "420" if yuv else "rgb"
+    src_type = args.get("src_type")
+    if src_type not in (None, "yuv420", "png"):
+        raise ValueError(f"unknown src_type {src_type!r}")
+    src_fmt = codec_fmt if src_type is None else ("420" if src_type == "yuv420" else "rgb")
     device = i_frame_net.dev
     reader = _reader(args, yuv)
     h, w = args["src_height"], args["src_width"]
-    stage = FrameStage(h, w, 16, yuv, zero_pad=False, frame_num=frame_num, device=device)
+    stage = FrameStage(h, w, 16, yuv, zero_pad=False, frame_num=frame_num, device=device, src_format=src_fmt)
     writer = None
     if args.get("save_decoded_frame"):   # test_video.py:84-88
-        writer = ReconWriter(args["recon_path"], h, w, "png" if args.get("src_type", "yuv420") == "png" else "yuv",
-                             "420" if yuv else "rgb", device)
+        writer = ReconWriter(args["recon_path"], h, w, "png" if src_fmt == "rgb" else "yuv", codec_fmt, device)
     ms = None
     if args.get("calc_ssim"):
         ms = MsSsim(h, w, frame_num, device) if yuv else MsSsimRGB(h, w, frame_num, device)
@@ -529,8 +554,8 @@ def run_test(p_frame_net, i_frame_net, args):
     dpb = None
     with torch.no_grad(), (writer if writer is not None else contextlib.nullcontext()):
         for frame_idx in range(frame_num):
-            frame = reader.read_one_frame(dst_format="420" if yuv else "rgb")
-            if frame is None or (yuv and frame[0] is None):
+            frame = reader.read_one_frame(dst_format=src_fmt)
+            if frame is None or (src_fmt == "420" and frame[0] is None):
                 raise ValueError(f"source ended at frame {frame_idx} of {frame_num}")
             dframe = stage.upload(frame)
             x = stage.load(dframe)
@@ -556,7 +581,9 @@ def run_test(p_frame_net, i_frame_net, args):
             stage.distortion(recon, dframe, frame_idx)
             if ms is not None:
                 from .dc.video_model import as_act
-                if yuv:
+                if stage.cross:
+                    ms.run_f32(as_act(recon), *stage.src_f32, frame_idx)
+                elif yuv:
                     ms.run(as_act(recon), dframe[0], dframe[1], frame_idx)
                 else:
                     ms.run(as_act(recon), dframe, frame_idx)

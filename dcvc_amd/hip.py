@@ -99,6 +99,11 @@ HIP_SYMBOLS = [
     ("dcvc_frame_sse_workspace", ctypes.c_int64, []),
     ("dcvc_frame_sse", _i, [_T, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     ("dcvc_recon_to_u8", _i, [_T, _i, _i, _i, _vp, _vp]),
+    ("dcvc_yuv420_to_rgb_nhwc", _i, [_vp, _vp, _i, _i, _T, _vp, _vp]),
+    ("dcvc_rgb_to_yuv420_planes", _i, [_vp, _i, _i, _vp, _vp, _vp]),
+    ("dcvc_yuv420f_to_nhwc", _i, [_vp, _vp, _i, _i, _T, _vp]),
+    ("dcvc_frame_sse_f32", _i, [_T, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    ("dcvc_recon_to_u8_cross", _i, [_T, _i, _i, _i, _vp, _vp]),
     ("dcvc_quadtree_encode_step", _i, [_T, _T, _T, _i, _T, _T, _vp, _vp, _f, _f, _vp]),
     ("dcvc_quadtree_indexes_step", _i, [_T, _T, _i, _vp, _f, _f, _vp]),
     ("dcvc_quadtree_decode_step", _i, [_T, _T, _i, _vp, _T, _T, _vp]),
@@ -123,6 +128,8 @@ HIP_SYMBOLS = [
     ("dcvc_down2_f64", _i, [_vp, _i, _i, _vp, _vp]),
     ("dcvc_rgb_planes_f64", _i, [_T, _vp, _i, _i, _vp, _vp, _vp]),
     ("dcvc_avgpool2_f64", _i, [_vp, _i, _i, _vp, _vp]),
+    ("dcvc_yuv_planes_f64_f32", _i, [_T, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    ("dcvc_rgb_planes_f64_f32", _i, [_T, _vp, _i, _i, _vp, _vp, _vp]),
     ("dcvc_debug_poison_lds", _i, [_i, _i, _vp]),
     ("dcvc_debug_poison_vgpr", _i, [_i, _vp]),
 ]
@@ -722,6 +729,36 @@ def yuv420_to_nhwc(y_u8, uv_u8, h, w, out):
     return out
 
 
+def yuv420_to_rgb_nhwc(y_u8, uv_u8, h, w, out, rgb_planes):
+    """uint8 device planes Y and U|V -> padded NHWC RGB fp32 and the planar
+    3 x h x w fp32 source (ycbcr420_to_rgb(order=1), functional.py:42-58)."""
+    assert y_u8.dtype == torch.uint8 and uv_u8.dtype == torch.uint8
+    assert y_u8.numel() == h * w and uv_u8.numel() == 2 * (h // 2) * (w // 2)
+    assert rgb_planes.dtype == torch.float32 and rgb_planes.numel() == 3 * h * w and rgb_planes.is_contiguous()
+    check(lib().dcvc_yuv420_to_rgb_nhwc(y_u8.data_ptr(), uv_u8.data_ptr(), h, w, out.c(), rgb_planes.data_ptr(),
+                                        stream()), "yuv420_to_rgb_nhwc")
+    return out
+
+
+def rgb_to_yuv420_planes(src_u8, h, w, y_f32, uv_f32):
+    """uint8 CHW RGB device frame -> fp32 planes Y (h*w) and U|V
+    (2*(h/2)*(w/2)) of rgb_to_ycbcr420 (functional.py:16-39)."""
+    assert src_u8.dtype == torch.uint8 and src_u8.numel() == 3 * h * w
+    assert y_f32.dtype == torch.float32 and uv_f32.dtype == torch.float32
+    assert y_f32.numel() == h * w and uv_f32.numel() == 2 * (h // 2) * (w // 2)
+    assert y_f32.is_contiguous() and uv_f32.is_contiguous()
+    check(lib().dcvc_rgb_to_yuv420_planes(src_u8.data_ptr(), h, w, y_f32.data_ptr(), uv_f32.data_ptr(), stream()),
+          "rgb_to_yuv420_planes")
+
+
+def yuv420f_to_nhwc(y_f32, uv_f32, h, w, out):
+    """yuv420_to_nhwc on fp32 planes (rgb_to_yuv420_planes' outputs)."""
+    assert y_f32.dtype == torch.float32 and uv_f32.dtype == torch.float32
+    assert y_f32.numel() == h * w and uv_f32.numel() == 2 * (h // 2) * (w // 2)
+    check(lib().dcvc_yuv420f_to_nhwc(y_f32.data_ptr(), uv_f32.data_ptr(), h, w, out.c(), stream()), "yuv420f_to_nhwc")
+    return out
+
+
 def frame_sse_workspace(device):
     n = int(lib().dcvc_frame_sse_workspace())
     return torch.empty(n // 8, dtype=torch.float64, device=device)
@@ -736,6 +773,28 @@ def frame_sse(x_hat, src_u8, h, w, workspace, out3, uv_u8=None):
     check(lib().dcvc_frame_sse(x_hat.c(), src_u8.data_ptr(), uv_u8.data_ptr() if yuv else None, h, w, int(yuv),
                                workspace.data_ptr(), out3.data_ptr(), stream()), "frame_sse")
     return out3
+
+
+def frame_sse_f32(x_hat, src_f32, h, w, workspace, out3, uv_f32=None):
+    """frame_sse against fp32 source planes (dcvc_frame_sse_f32)."""
+    assert x_hat.dtype == F32 and x_hat.C == 3 and out3.dtype == torch.float64 and out3.numel() >= 3
+    yuv = uv_f32 is not None
+    assert src_f32.dtype == torch.float32 and src_f32.numel() == (h * w if yuv else 3 * h * w)
+    assert not yuv or (uv_f32.dtype == torch.float32 and uv_f32.numel() == 2 * (h // 2) * (w // 2))
+    check(lib().dcvc_frame_sse_f32(x_hat.c(), src_f32.data_ptr(), uv_f32.data_ptr() if yuv else None, h, w, int(yuv),
+                                   workspace.data_ptr(), out3.data_ptr(), stream()), "frame_sse_f32")
+    return out3
+
+
+def recon_to_u8_cross(x_hat, h, w, to_rgb, out):
+    """Decoded frame -> uint8 for the writer of the other format
+    (dcvc_recon_to_u8_cross): a YCbCr 4:4:4 frame as HWC RGB (to_rgb), or an
+    RGB frame as Y | U | V planes."""
+    n = 3 * h * w if to_rgb else h * w + 2 * (h // 2) * (w // 2)
+    assert out.dtype == torch.uint8 and out.numel() >= n and x_hat.dtype == F32 and x_hat.C == 3
+    check(lib().dcvc_recon_to_u8_cross(x_hat.c(), h, w, 1 if to_rgb else 0, out.data_ptr(), stream()),
+          "recon_to_u8_cross")
+    return out
 
 
 def recon_to_u8(x_hat, h, w, yuv420, out):
@@ -765,6 +824,25 @@ def rgb_planes_f64(x_hat, src_u8, h, w, src, rec):
     assert src.numel() >= 3 * h * w and rec.numel() >= 3 * h * w
     check(lib().dcvc_rgb_planes_f64(x_hat.c(), src_u8.data_ptr(), h, w, src.data_ptr(), rec.data_ptr(), stream()),
           "rgb_planes_f64")
+
+
+def yuv_planes_f64_f32(x_hat, y_f32, uv_f32, h, w, src, rec):
+    """yuv_planes_f64 with fp32 source planes."""
+    n = h * w + 2 * (h // 2) * (w // 2)
+    assert src.dtype == torch.float64 and rec.dtype == torch.float64 and src.numel() >= n and rec.numel() >= n
+    assert y_f32.dtype == torch.float32 and uv_f32.dtype == torch.float32
+    assert y_f32.numel() == h * w and uv_f32.numel() == 2 * (h // 2) * (w // 2)
+    check(lib().dcvc_yuv_planes_f64_f32(x_hat.c(), y_f32.data_ptr(), uv_f32.data_ptr(), h, w, src.data_ptr(),
+                                        rec.data_ptr(), stream()), "yuv_planes_f64_f32")
+
+
+def rgb_planes_f64_f32(x_hat, src_f32, h, w, src, rec):
+    """rgb_planes_f64 with a planar fp32 source (3 x h x w)."""
+    assert src.dtype == torch.float64 and rec.dtype == torch.float64
+    assert src.numel() >= 3 * h * w and rec.numel() >= 3 * h * w
+    assert src_f32.dtype == torch.float32 and src_f32.numel() == 3 * h * w
+    check(lib().dcvc_rgb_planes_f64_f32(x_hat.c(), src_f32.data_ptr(), h, w, src.data_ptr(), rec.data_ptr(),
+                                        stream()), "rgb_planes_f64_f32")
 
 
 def avgpool2_f64(x, h, w, y):

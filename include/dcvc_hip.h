@@ -302,6 +302,44 @@ int dcvc_recon_to_u8(dcvc_tensor x_hat, int h, int w, int yuv420, uint8_t *out,
                      void *stream);
 
 /*
+ * Cross-format sources and writers (crossfmt.hip): run_test's source format
+ * and codec format are independent (DCVC-DC/test_video.py:79-119); the
+ * reference's readers convert with src/transforms/functional.py:16-58.  All
+ * results are bit-equal to the reference's numpy / scipy values.  h, w even.
+ *
+ * YUV420 source for an RGB codec: ycbcr420_to_rgb(y / 255, uv / 255, order=1)
+ * (chroma upsampled as scipy.ndimage.zoom(uv, (1, 2, 2), order=1), BT.709 in
+ * fp32, clip) -> out: fp32 NHWC RGB replicate-padded to out's size, and
+ * rgb_planes: the same values as planar 3 x h x w fp32 (device), the source
+ * the distortion and MS-SSIM compare against.
+ */
+int dcvc_yuv420_to_rgb_nhwc(const uint8_t *y, const uint8_t *uv, int h, int w,
+                            dcvc_tensor out, float *rgb_planes, void *stream);
+/* RGB source for a YUV420 codec, step 1: rgb_to_ycbcr420(rgb / 255) of a
+ * uint8 CHW frame -> fp32 planes y_plane (h x w) and uv_planes
+ * (2 x h/2 x w/2), both clipped to [0, 1] (device). */
+int dcvc_rgb_to_yuv420_planes(const uint8_t *rgb, int h, int w, float *y_plane,
+                              float *uv_planes, void *stream);
+/* Step 2: dcvc_yuv420_to_nhwc on fp32 planes (ycbcr420_to_444(order=0) and
+ * replicate padding to out's size). */
+int dcvc_yuv420f_to_nhwc(const float *y, const float *uv, int h, int w,
+                         dcvc_tensor out, void *stream);
+/* dcvc_frame_sse against fp32 source planes (planar 3 x h x w RGB for
+ * yuv420 = 0; Y and U|V planes for yuv420 = 1): same in-place clamp, same
+ * arithmetic and summation order, same workspace. */
+int dcvc_frame_sse_f32(dcvc_tensor x_hat, const float *src, const float *uv,
+                       int h, int w, int yuv420, double *workspace,
+                       double *out3, void *stream);
+/* The cross cases of the decoded-frame writers, into out (device uint8):
+ *   to_rgb = 1: x_hat holds YCbCr 4:4:4; PNGWriter's h x w x 3 RGB of
+ *               ycbcr420_to_rgb(ycbcr444_to_420(x_hat), order=1);
+ *   to_rgb = 0: x_hat holds RGB; YUVWriter's Y plane then U, V planes of
+ *               rgb_to_ycbcr420(x_hat).
+ * Quantised as clip(rint(v * 255), 0, 255) like dcvc_recon_to_u8. */
+int dcvc_recon_to_u8_cross(dcvc_tensor x_hat, int h, int w, int to_rgb,
+                           uint8_t *out, void *stream);
+
+/*
  * Quadtree (four-part) prior step k, encoder side
  * (forward_four_part_prior write=True, DCVC-DC/src/models/common_model.py:
  * 142-252).  y: latent (C ch, fp32); params: common_params (3C ch:
@@ -434,6 +472,15 @@ int dcvc_down2_f64(const double *in, int h, int w, double *out, void *stream);
 int dcvc_rgb_planes_f64(dcvc_tensor x_hat, const uint8_t *src, int h, int w,
                         double *src_planes, double *rec_planes, void *stream);
 int dcvc_avgpool2_f64(const double *in, int h, int w, double *out, void *stream);
+/* dcvc_yuv_planes_f64 / dcvc_rgb_planes_f64 with the fp32 source planes of
+ * the cross-format ingest (dcvc_rgb_to_yuv420_planes' y | uv,
+ * dcvc_yuv420_to_rgb_nhwc's rgb_planes) in place of a uint8 source. */
+int dcvc_yuv_planes_f64_f32(dcvc_tensor x_hat, const float *y, const float *uv,
+                            int h, int w, double *src_planes,
+                            double *rec_planes, void *stream);
+int dcvc_rgb_planes_f64_f32(dcvc_tensor x_hat, const float *src, int h, int w,
+                            double *src_planes, double *rec_planes,
+                            void *stream);
 
 /* Debug aid: fill the LDS of `blocks` workgroups with all-ones bytes (NaN in
  * bf16 / fp32), to expose kernels that read LDS they never wrote
