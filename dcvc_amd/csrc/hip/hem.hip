@@ -130,10 +130,26 @@ __device__ __forceinline__ float probs_to_bits(float p) {
   const float b = -1.f * logf(p + 1e-5f) / 0.6931471805599453f;  // LowerBound(bits, 0)
   return b > 0.f ? b : 0.f;
 }
-__device__ __forceinline__ float dist_cdf(int gaussian, float v, float s) {
-  if (gaussian) return 0.5f * (1.f + erff(v * (1.f / s) / 1.4142135623730951f));
-  const float sg = v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f);
-  return 0.5f - 0.5f * sg * expm1f(-fabsf(v) / s);
+// P(yq - 0.5 < X < yq + 0.5), X ~ Normal(0, s) / Laplace(0, s): the reference's
+// cdf(yq + 0.5) - cdf(yq - 0.5) (common_model.py get_y_*_bits).  Taken
+// literally in fp32 that difference carries one rounding of a CDF next to 1
+// (2^-24) whatever its own size, which at p ~ 1e-5 is 9e-3 bits.  The density
+// is even, so |yq| stands for yq, and each branch below subtracts only where
+// nothing cancels: the result is good to a few ulp of p itself.
+__device__ __forceinline__ float bin_prob(int gaussian, float yq, float s) {
+  const float a = fabsf(yq);
+  if (gaussian) {
+    const float r = (1.f / s) / 1.4142135623730951f;
+    if (a < 0.5f) return erff(0.5f * r);
+    if (r < 0.03125f) {  // a narrow bin: the density's integral about its midpoint m, to O(r^4)
+      const float m = a * r;
+      return 0.5641895835477563f * r * expf(-m * m) * (1.f + r * r * (2.f * m * m - 1.f) * (1.f / 12.f));
+    }
+    const float lo = (a - 0.5f) * r, hi = (a + 0.5f) * r;
+    return lo < 1.f ? 0.5f * (erff(hi) - erff(lo)) : 0.5f * (erfcf(lo) - erfcf(hi));
+  }
+  if (a < 0.5f) return -expm1f(-0.5f / s);
+  return 0.5f * expf(-(a - 0.5f) / s) * -expm1f(-1.f / s);  // (e^(-(a-.5)/s) - e^(-(a+.5)/s)) / 2
 }
 
 // estimate mode: y_hat outputs + per-site bits (get_y_laplace_bits with
@@ -152,7 +168,7 @@ __global__ void dp_estimate_kernel(DP t, int k, float *bits, int gaussian, float
   const float yv = ld<float>(t.y.p, pix * t.y.cs + t.y.co + ch) / qs;
   const float yq = rintf(yv - me);
   const float s = fminf(fmaxf(sc, smin), 1e10f);
-  bits[i] = probs_to_bits(dist_cdf(gaussian, yq + 0.5f, s) - dist_cdf(gaussian, yq - 0.5f, s));
+  bits[i] = probs_to_bits(bin_prob(gaussian, yq, s));
   dp_store(t, k, pix, ch, other, yq + me, qs);
 }
 

@@ -26,7 +26,9 @@ pytestmark = pytest.mark.gpu
 # max |PSNR - oracle PSNR| in dB (random-weight sequences, PSNR ~6-7 dB)
 PARITY_TOL = {"sym_frac": 2e-3, "bits_rel": 5e-3, "psnr_db": 1e-4}
 # split precision (the bench's) in estimate mode: the float bit estimates of
-# the free-running golden sequences, measured within 4e-7 of the reference's
+# the free-running golden sequences, measured within 2.2e-6 of the reference's
+# (the kernels' bin probability has none of the fp32 cancellation of the
+# reference's cdf(y + 0.5) - cdf(y - 0.5): they sit nearer the exact value)
 # (gpurun_out/parity_dc.json estimate_split_*); 1e-5 leaves no room for a
 # regression of the estimate path.  Parity mode keeps PARITY_TOL: its fp32
 # chain flips one tie of golden B frame 1 and frame 2 then codes a slightly
