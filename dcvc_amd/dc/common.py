@@ -38,12 +38,21 @@ class SymbolBuffer:
     def idx_slice(self, i):
         return self.idx[self.offs[i]:self.offs[i + 1]]
 
-    def to_host(self):
+    def to_host(self, then=None):
+        """``then`` (optional): GPU work to enqueue behind the download (the
+        encoder-side reconstruction).  Only the download is waited for, so
+        that work runs while the host codes the symbols."""
         s = K.pinned("sb_sym", self.sym.numel(), self.sym_dtype)
         x = K.pinned("sb_idx", self.idx.numel(), torch.int16)
         s.copy_(self.sym, non_blocking=K.ASYNC_COPIES)
         x.copy_(self.idx, non_blocking=K.ASYNC_COPIES)
-        torch.cuda.current_stream().synchronize()
+        if then is None:
+            torch.cuda.current_stream().synchronize()
+        else:
+            done = torch.cuda.Event()
+            done.record()
+            then()
+            done.synchronize()
         s, x = s.numpy(), x.numpy()
         return [(s[self.offs[i]:self.offs[i + 1]], x[self.offs[i]:self.offs[i + 1]]) for i in range(len(self.sizes))]
 

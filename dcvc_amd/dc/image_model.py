@@ -9,9 +9,9 @@ import torch
 
 from .. import hip as K
 from ..hip import F32, ACT_LRELU, ACT_CLAMP01
-from ..layers import split_guarded, split_checkpoint, Ctx, Precision, DepthConvBlock, ResidualBlockWithStride, ResidualBlockUpsample, UNet
+from ..layers import split_guarded, split_checkpoint, frame_encoder, frame_decoder, Ctx, Precision, DepthConvBlock, ResidualBlockWithStride, ResidualBlockUpsample, UNet
 from ..entropy import ScaleTable, FactorizedTable, EntropyCoder
-from ..stream_helper import get_downsampled_shape, encode_i, decode_i, filesize, get_state_dict
+from ..stream_helper import get_downsampled_shape, encode_i, decode_i, pack_i, unpack_i, filesize, get_state_dict
 from .common import SymbolBuffer, QuadtreePrior, BitCounter, bits_result, pad_for_y, crop_to, q_fine, curr_q
 from .video_model import as_act
 
@@ -145,10 +145,12 @@ class IntraNoAR:
         return {"x_hat": x_hat.nchw_view(), "bit": r["bit"], "bpp": r["bpp"], "bpp_y": r["bpp_y"],
                 "bpp_z": r["bpp_z"]}
 
-    def compress(self, x, q_in_ckpt, q_index):
-        """image_model.py:198-229 (without the unused encoder recon)."""
+    def compress(self, x, q_in_ckpt, q_index, recon=False):
+        """image_model.py:198-229 (without the unused encoder recon;
+        ``recon=True`` computes it behind the symbol download and returns it
+        as ``x_hat``, an Act as ``decompress`` returns it)."""
         x = as_act(x)
-        q_enc, _ = self.get_q_for_inference(q_in_ckpt, q_index)
+        q_enc, q_dec = self.get_q_for_inference(q_in_ckpt, q_index)
         y, z_hat = self._analysis(x, q_enc)
         yh, yw = y.H, y.W
         params = self._params(z_hat, yh, yw)
@@ -157,15 +159,20 @@ class IntraNoAR:
         c_y = [sb.plan("y", self.N // 4 * yh * yw) for _ in range(4)]
         sb.alloc()
         K.to_symbols(z_hat, sb.sym_slice(c_z))
-        self.prior.encode(y, params, sb, c_y, self.scale_table)
-        host = sb.to_host()
+        y_hat = self.prior.encode(y, params, sb, c_y, self.scale_table)
+        out = {"x_hat": None}
+
+        def reconstruct():
+            out["x_hat"] = self._decode_image(y_hat, q_dec)
+        host = sb.to_host(reconstruct if recon else None)
         ec = self.entropy_coder
         ec.reset()
         ec.encode(host[c_z][0], self.z_table.indexes(z_hat.H, z_hat.W), self.z_table.table)
         for c in c_y:
             ec.encode(host[c][0], host[c][1], self.scale_table.table)
         ec.flush()
-        return {"bit_stream": ec.get_encoded_stream(), "x_hat": None}
+        out["bit_stream"] = ec.get_encoded_stream()
+        return out
 
     def decompress(self, bit_stream, height, width, q_in_ckpt, q_index):
         """image_model.py:231-252."""
@@ -180,6 +187,25 @@ class IntraNoAR:
         params = self._params(z_hat, yh, yw)
         y_hat = self.prior.decode(params, lambda idx: ec.decode(idx, self.scale_table.table), self.scale_table)
         return {"x_hat": self._decode_image(y_hat, q_dec)}
+
+    @frame_encoder
+    def encode_frame(self, x, q_in_ckpt, q_index, pic_height, pic_width):
+        """Encoder only: {"payload": the bytes of the reference-format frame
+        file (pack_i), "x_hat": the encoder's own reconstruction, "bit",
+        "precision_fallback"} (layers.frame_encoder)."""
+        enc = self.compress(x, q_in_ckpt, q_index, recon=True)
+        payload = pack_i(pic_height, pic_width, q_in_ckpt, q_index, enc["bit_stream"])
+        return {"payload": payload, "x_hat": enc["x_hat"].nchw_view(), "bit": len(payload) * 8}
+
+    @frame_decoder
+    def decode_frame(self, payload, dpb=None, height=None, width=None):
+        """Decoder only: {"x_hat"} from a frame's bytes, which carry the
+        picture size (``dpb`` is unused; ``height`` / ``width``, when given,
+        must agree with the payload)."""
+        h, w, q_in_ckpt, q_index, bit_stream = unpack_i(payload)
+        if (height is not None and height != h) or (width is not None and width != w):
+            raise ValueError(f"frame says {h}x{w}, caller {height}x{width}")
+        return {"x_hat": self.decompress(bit_stream, h, w, q_in_ckpt, q_index)["x_hat"].nchw_view()}
 
     @split_guarded
     def encode_decode(self, x, q_in_ckpt, q_index, output_path=None, pic_width=None, pic_height=None):

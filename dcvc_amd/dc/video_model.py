@@ -15,10 +15,10 @@ import torch
 
 from .. import hip as K
 from ..hip import F32, ACT_LRELU, ACT_CLAMP01
-from ..layers import (split_guarded, split_checkpoint, Ctx, Precision, DepthConvBlock, ResidualBlockWithStride, ResidualBlockUpsample,
+from ..layers import (split_guarded, split_checkpoint, frame_encoder, frame_decoder, Ctx, Precision, DepthConvBlock, ResidualBlockWithStride, ResidualBlockUpsample,
                       ResBlock, UNet, SpyNet, Grids, hyper_enc, hyper_dec, cast)
 from ..entropy import ScaleTable, FactorizedTable, EntropyCoder
-from ..stream_helper import (get_downsampled_shape, encode_p, decode_p, filesize, get_state_dict)
+from ..stream_helper import (get_downsampled_shape, encode_p, decode_p, pack_p, unpack_p, filesize, get_state_dict)
 from .common import SymbolBuffer, QuadtreePrior, BitCounter, bits_result, pad_for_y, crop_to, q_fine, curr_q
 
 G1, G2, G4, G8, G16 = 48, 64, 96, 96, 128  # video_model.py:19-23
@@ -331,10 +331,13 @@ class DMC:
         return x_hat, feature
 
     # --------------------------------------------------------------- codec
-    def compress(self, x, dpb, q_in_ckpt, q_index, frame_idx):
+    def compress(self, x, dpb, q_in_ckpt, q_index, frame_idx, recon=False):
         """video_model.py:425-481.  Returns {"bit_stream": bytes, "dpb": None}
         (the encoder-side reconstruction is not computed: write mode returns
-        the decoder's dpb, which is bit-identical)."""
+        the decoder's dpb, which is bit-identical).  ``recon=True`` computes
+        it, from the y_hat / mv_y_hat of the prior encoders, and returns the
+        dpb ``decompress`` would return; its kernels are enqueued behind the
+        symbol download, so they run while the host codes the frame."""
         x = as_act(x)
         dpb = dpb_in(dpb)
         mv_q_enc, mv_q_dec, y_q_enc, y_q_dec = self.get_q_for_inference(q_in_ckpt, q_index)
@@ -354,14 +357,20 @@ class DMC:
         sb.alloc()
         K.to_symbols(mv_z_hat, sb.sym_slice(c_mvz))
         mv_y_hat = self.mv_prior.encode(mv_y, mv_params, sb, c_mv, self.scale_table)
-        mv_hat, _ = self._mv_decoder(mv_y_hat, mv_q_dec)
+        mv_hat, mv_feature = self._mv_decoder(mv_y_hat, mv_q_dec)
         ctx = self._motion_compensation(dpb, mv_hat, frame_idx)
         y = self._contextual_encoder(x, ctx, y_q_enc)
         z_hat = self.y_henc(pad_for_y(y))
         K.to_symbols(z_hat, sb.sym_slice(c_z))
         params = self._res_prior_params(z_hat, dpb, ctx.c3, yh, yw)
-        self.y_prior.encode(y, params, sb, c_y, self.scale_table)
-        host = sb.to_host()
+        y_hat = self.y_prior.encode(y, params, sb, c_y, self.scale_table)
+        out = {"dpb": None}
+
+        def reconstruct():
+            x_hat, feature = self._recon(y_hat, ctx, y_q_dec)
+            out["dpb"] = {"ref_frame": x_hat.nchw_view(), "ref_feature": feature, "ref_mv_feature": mv_feature,
+                          "ref_y": y_hat, "ref_mv_y": mv_y_hat}
+        host = sb.to_host(reconstruct if recon else None)
 
         ec = self.entropy_coder
         ec.reset()
@@ -371,7 +380,8 @@ class DMC:
         for c in c_mv + c_y:
             ec.encode(host[c][0], host[c][1], self.scale_table.table)
         ec.flush()
-        return {"dpb": None, "bit_stream": ec.get_encoded_stream()}
+        out["bit_stream"] = ec.get_encoded_stream()
+        return out
 
     def decompress(self, dpb, string, height, width, q_in_ckpt, q_index, frame_idx):
         """video_model.py:483-520."""
@@ -402,6 +412,22 @@ class DMC:
         x_hat, feature = self._recon(y_hat, ctx, y_q_dec)
         return {"dpb": {"ref_frame": x_hat.nchw_view(), "ref_feature": feature, "ref_mv_feature": mv_feature,
                         "ref_y": y_hat, "ref_mv_y": mv_y_hat}}
+
+    @frame_encoder
+    def encode_frame(self, x, dpb, q_in_ckpt, q_index, frame_idx):
+        """Encoder only: {"payload": the bytes of the reference-format frame
+        file (pack_p), "dpb": the encoder's own reconstruction, "bit",
+        "precision_fallback"} (layers.frame_encoder)."""
+        enc = self.compress(x, dpb, q_in_ckpt, q_index, frame_idx, recon=True)
+        payload = pack_p(enc["bit_stream"], q_in_ckpt, q_index, frame_idx)
+        return {"payload": payload, "dpb": enc["dpb"], "bit": len(payload) * 8}
+
+    @frame_decoder
+    def decode_frame(self, payload, dpb, height, width):
+        """Decoder only: {"dpb"} from a frame's bytes and the decoder's own
+        dpb (layers.frame_decoder: ``fallback`` selects the fp32 twin)."""
+        q_in_ckpt, q_index, frame_idx, string = unpack_p(payload)
+        return self.decompress(dpb, string, height, width, q_in_ckpt, q_index, frame_idx)
 
     def forward_one_frame(self, x, dpb, q_in_ckpt=False, q_index=None, frame_idx=0):
         """Estimate mode, video_model.py:559-628: the encoder graph with the

@@ -680,3 +680,112 @@ def run_test_hem(video_net, i_frame_net, args, device=None):
     log = generate_log_json_hem(frame_num, frame_types, bits, psnrs, mv, h * w, time.time() - start_time)
     log["msssim_unpinned"] = True   # pytorch_msssim's algorithm, package absent (MsSsimRGB)
     return log
+
+
+# ------------------------------------------- stand-alone encoder / decoder
+def _tag_format(nets, args):
+    """``dist_in_yuv420`` in args is the caller's statement of which
+    checkpoints the nets hold; the sequence drivers check it against the file."""
+    if "dist_in_yuv420" in args:
+        for net in nets:
+            net.codec_format = "yuv420" if args["dist_in_yuv420"] else "rgb"
+
+
+def encode_video(i_frame_net, p_frame_net, args):
+    """Encoder only: ``run_test`` / ``run_test_hem`` (their keys, readers,
+    FrameStage, both source formats) with the frames coded by a
+    ``sequence.SequenceEncoder`` into the one file ``args["seq_path"]``
+    instead of ``encode_decode`` and a bin folder; ``args["digest"]`` (default
+    True) stores the DPB digests.  Nothing is decoded: the log's bits are the
+    frames' payload bits and its PSNR is that of the ENCODER's reconstruction
+    (which a decoder of the file reproduces bit for bit)."""
+    from .sequence import SequenceEncoder, codec_of
+    hem = codec_of(i_frame_net) == "HEM"
+    _tag_format((i_frame_net, p_frame_net), args)
+    frame_num, gop_size = args["frame_num"], args["gop_size"]
+    verbose = args.get("verbose", 0)
+    yuv = bool(args.get("dist_in_yuv420", False)) and not hem
+    codec_fmt = "420" if yuv else "rgb"
+    src_type = args.get("src_type")
+    if src_type not in (None, "yuv420", "png"):
+        raise ValueError(f"unknown src_type {src_type!r}")
+    src_fmt = codec_fmt if src_type is None else ("420" if src_type == "yuv420" else "rgb")
+    if hem and src_fmt != "rgb":
+        raise ValueError("the HEM harness reads RGB sources")
+    device = i_frame_net.dev
+    reader = _reader({**args, "src_type": src_type or "png"} if hem else args, yuv)
+    h, w = args["src_height"], args["src_width"]
+    if hem:
+        stage = FrameStage(h, w, 64, False, zero_pad=True, frame_num=frame_num, device=device)
+        q = dict(i_frame_q_scale=args["i_frame_q_scale"], p_frame_mv_y_q_scale=args["p_frame_mv_y_q_scale"],
+                 p_frame_y_q_scale=args["p_frame_y_q_scale"])
+    else:
+        stage = FrameStage(h, w, 16, yuv, zero_pad=False, frame_num=frame_num, device=device, src_format=src_fmt)
+        q = dict(q_in_ckpt=args["q_in_ckpt"], q_index=args["i_frame_q_index"])
+    frame_types, bits, fallbacks = [], [], []
+    start_time = time.time()
+    with SequenceEncoder(i_frame_net, p_frame_net, args["seq_path"], w, h, gop_size, yuv420=yuv,
+                         digest=bool(args.get("digest", True)), **q) as enc:
+        for frame_idx in range(frame_num):
+            frame = reader.read_one_frame(dst_format=src_fmt)
+            if frame is None or (src_fmt == "420" and frame[0] is None):
+                raise ValueError(f"source ended at frame {frame_idx} of {frame_num}")
+            dframe = stage.upload(frame)
+            out = enc.encode(stage.load(dframe))
+            frame_types.append(0 if out["type"] == "I" else 1)
+            bits.append(out["bit"])
+            fallbacks.append(out["precision_fallback"])
+            stage.distortion(out["recon"], dframe, frame_idx)
+            if verbose >= 2:
+                print(f"frame {frame_idx}, bits: {bits[-1]:.3f}", flush=True)
+    sse = stage.sums()
+    test_time = time.time() - start_time
+    zeros = [0.0] * frame_num
+    if hem:
+        log = generate_log_json_hem(frame_num, frame_types, bits, [psnr_rgb(sse[i], h, w) for i in range(frame_num)],
+                                    zeros, h * w, test_time)
+    elif yuv:
+        per = [psnr_yuv(sse[i], h, w) for i in range(frame_num)]
+        log = generate_log_json(frame_num, h * w, test_time, frame_types, bits, [p[3] for p in per], zeros,
+                                [p[0] for p in per], [p[1] for p in per], [p[2] for p in per], zeros, zeros, zeros,
+                                verbose=verbose >= 1)
+    else:
+        log = generate_log_json(frame_num, h * w, test_time, frame_types, bits,
+                                [psnr_rgb(sse[i], h, w) for i in range(frame_num)], zeros, verbose=verbose >= 1)
+    log["frame_bits"] = bits
+    log["precision_fallbacks"] = fallbacks
+    return log
+
+
+def decode_video(i_frame_net, p_frame_net, args):
+    """Decoder only: decodes ``args["seq_path"]`` with a
+    ``sequence.SequenceDecoder`` (which verifies the stored DPB digests) and,
+    with ``save_decoded_frame``, writes the frames as ``run_test`` /
+    ``run_test_hem`` write them (``recon_path`` / ``decoded_frame_folder``;
+    ``src_type`` selects PNG or out.yuv as there, the codec's own format by
+    default).  Returns the per-frame bits and types."""
+    from .sequence import SequenceDecoder, codec_of
+    hem = codec_of(i_frame_net) == "HEM"
+    _tag_format((i_frame_net, p_frame_net), args)
+    frame_types, bits = [], []
+    start_time = time.time()
+    with SequenceDecoder(i_frame_net, p_frame_net, args["seq_path"]) as dec:
+        h, w = dec.height, dec.width
+        codec_fmt = "420" if dec.reader.format == "yuv420" else "rgb"
+        src_type = args.get("src_type")
+        src_fmt = codec_fmt if src_type is None else ("420" if src_type == "yuv420" else "rgb")
+        writer = None
+        if args.get("save_decoded_frame"):
+            if hem:
+                writer = ReconWriter(args["decoded_frame_folder"], h, w, "hem_png", "rgb", i_frame_net.dev)
+            else:
+                writer = ReconWriter(args["recon_path"], h, w, "png" if src_fmt == "rgb" else "yuv", codec_fmt,
+                                     i_frame_net.dev)
+        with (writer if writer is not None else contextlib.nullcontext()):
+            for frame_idx, out in enumerate(dec):
+                frame_types.append(0 if out["type"] == "I" else 1)
+                bits.append(out["bit"])
+                if writer is not None:
+                    writer.write(out["x_hat"], frame_idx)
+    return {"frame_num": len(bits), "frame_pixel_num": h * w, "frame_type": frame_types, "frame_bits": bits,
+            "test_time": time.time() - start_time}

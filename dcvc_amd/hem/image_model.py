@@ -9,14 +9,14 @@ import torch
 
 from .. import hip as K
 from ..hip import F32, ACT_CLAMP01
-from ..layers import split_guarded, split_checkpoint, Ctx, Precision, hyper_enc, hyper_dec
+from ..layers import split_guarded, split_checkpoint, frame_encoder, frame_decoder, Ctx, Precision, hyper_enc, hyper_dec
 from ..entropy import ScaleTable, FactorizedTable
 from ..stream_helper import get_downsampled_shape, filesize, get_state_dict
 from ..dc.common import SymbolBuffer, BitCounter, bits_result
 from ..dc.video_model import as_act
 from .common import DualPrior, HemEntropyCoder, lower_bound_q, get_rounded_q
 from .layers import EncTower, DecTower, UNet, Seq3, chunk3_to_buffer_order
-from .stream_helper import encode_i, decode_i
+from .stream_helper import encode_i, decode_i, pack_i, unpack_i
 
 
 class IntraNoAR:
@@ -94,8 +94,10 @@ class IntraNoAR:
         f = self.refine_unet(f)
         return K.conv(self.refine_conv, f, out_dtype=F32, act=ACT_CLAMP01 if clamp else K.ACT_NONE)
 
-    def compress(self, x, q_scale):
-        """image_model.py:134-157."""
+    def compress(self, x, q_scale, recon=False):
+        """image_model.py:134-157.  ``recon=True`` also returns ``x_hat``
+        (an Act, as ``decompress`` returns it), computed behind the symbol
+        download while the host codes the frame."""
         x = as_act(x)
         q = self._q(q_scale)
         y, z_hat = self._analysis(x, q)
@@ -106,15 +108,40 @@ class IntraNoAR:
         sb.alloc()
         K.to_symbols_i32(z_hat, sb.sym_slice(c_z))
         buf = self._params(z_hat)
-        self.prior.encode(y, buf, q, [sb.sym_slice(c) for c in c_y], [sb.idx_slice(c) for c in c_y],
-                          self.scale_table)
-        host = sb.to_host()
+        y_hat = self.prior.encode(y, buf, q, [sb.sym_slice(c) for c in c_y], [sb.idx_slice(c) for c in c_y],
+                                  self.scale_table)
+        out = {}
+
+        def reconstruct():
+            out["x_hat"] = self._synthesis(y_hat, clamp=True)
+        host = sb.to_host(reconstruct if recon else None)
         ec = self.entropy_coder
         ec.reset_encoder()
         ec.encode(host[c_z][0], self.z_table.indexes(z_hat.H, z_hat.W).astype("int32"), self.z_table.table)
         for c in c_y:
             ec.encode(host[c][0], host[c][1].astype("int32"), self.scale_table.table)
-        return {"bit_stream": ec.flush_encoder()}
+        out["bit_stream"] = ec.flush_encoder()
+        return out
+
+    @frame_encoder
+    def encode_frame(self, x, q_scale, pic_height, pic_width):
+        """Encoder only: {"payload": the bytes of the reference-format frame
+        file (pack_i), "x_hat": the encoder's own reconstruction, "bit",
+        "precision_fallback"} (layers.frame_encoder)."""
+        q_scale, q_index = get_rounded_q(q_scale)
+        enc = self.compress(x, q_scale, recon=True)
+        payload = pack_i(pic_height, pic_width, q_index, enc["bit_stream"])
+        return {"payload": payload, "x_hat": enc["x_hat"].nchw_view(), "bit": len(payload) * 8}
+
+    @frame_decoder
+    def decode_frame(self, payload, dpb=None, height=None, width=None):
+        """Decoder only: {"x_hat"} from a frame's bytes, which carry the
+        picture size (``dpb`` is unused; ``height`` / ``width``, when given,
+        must agree with the payload)."""
+        h, w, q_index, bit_stream = unpack_i(payload)
+        if (height is not None and height != h) or (width is not None and width != w):
+            raise ValueError(f"frame says {h}x{w}, caller {height}x{width}")
+        return {"x_hat": self.decompress(bit_stream, h, w, q_index / 100)["x_hat"].nchw_view()}
 
     def decompress(self, bit_stream, height, width, q_scale):
         """image_model.py:159-171."""

@@ -15,14 +15,14 @@ import torch
 
 from .. import hip as K
 from ..hip import F32, ACT_LRELU, ACT_CLAMP01
-from ..layers import split_guarded, split_checkpoint, Ctx, Precision, SpyNet, Grids, ResidualBlockWithStride, hyper_enc, hyper_dec
+from ..layers import split_guarded, split_checkpoint, frame_encoder, frame_decoder, Ctx, Precision, SpyNet, Grids, ResidualBlockWithStride, hyper_enc, hyper_dec
 from ..entropy import ScaleTable, FactorizedTable
 from ..stream_helper import get_downsampled_shape, filesize, get_state_dict
 from ..dc.common import SymbolBuffer, BitCounter, bits_result
 from ..dc.video_model import as_act, dpb_in, Contexts
 from .common import DualPrior, HemEntropyCoder, lower_bound_q, get_rounded_q
 from .layers import ResBlock, EncTower, DecTower, UNet, Seq3, chunk3_to_buffer_order
-from .stream_helper import encode_p, decode_p
+from .stream_helper import encode_p, decode_p, pack_p, unpack_p
 
 CH_MV, CH_N, CH_M = 64, 64, 96  # video_model.py:140-142
 
@@ -236,8 +236,11 @@ class DMC:
         return mv_z_hat, mv_y_hat, z_hat, y_hat, ctx
 
     # --------------------------------------------------------------- codec
-    def compress(self, x, dpb, mv_y_q_scale, y_q_scale):
-        """video_model.py:263-330 without the discarded reconstruction."""
+    def compress(self, x, dpb, mv_y_q_scale, y_q_scale, recon=False):
+        """video_model.py:263-330 without the discarded reconstruction.
+        ``recon=True`` computes it behind the symbol download (it runs while
+        the host codes the frame) and returns the dpb ``decompress`` would
+        return, under "dpb"."""
         x = as_act(x)
         dpb = dpb_in(dpb)
         mvq, yq = self._q(mv_y_q_scale, y_q_scale)
@@ -259,10 +262,18 @@ class DMC:
         def y_prior(y, buf):
             return self.y_prior.encode(y, buf, yq, [sb.sym_slice(c) for c in c_y], [sb.idx_slice(c) for c in c_y],
                                        st)
-        mv_z_hat, _, z_hat, _, _ = self._analysis(x, dpb, mvq, yq, mv_prior, y_prior)
+        mv_z_hat, mv_y_hat, z_hat, y_hat, ctx = self._analysis(x, dpb, mvq, yq, mv_prior, y_prior)
         K.to_symbols_i32(mv_z_hat, sb.sym_slice(c_mvz))
         K.to_symbols_i32(z_hat, sb.sym_slice(c_z))
-        host = sb.to_host()
+        out = {}
+
+        def reconstruct():
+            x_hat, feature = self._recon(y_hat, ctx)
+            out["dpb"] = {"ref_frame": x_hat.nchw_view(), "ref_feature": feature, "ref_y": y_hat,
+                          "ref_mv_y": mv_y_hat}
+        host = sb.to_host(reconstruct if recon else None)
+        if not recon:
+            out["dbp"] = None
         ec = self.entropy_coder
         ec.reset_encoder()
         ec.encode(host[c_mvz][0], self.mvz_table.indexes(zh, zw).astype("int32"), self.mvz_table.table)
@@ -271,7 +282,27 @@ class DMC:
         ec.encode(host[c_z][0], self.z_table.indexes(zh, zw).astype("int32"), self.z_table.table)
         for c in c_y:
             ec.encode(host[c][0], host[c][1].astype("int32"), st.table)
-        return {"dbp": None, "bit_stream": ec.flush_encoder()}
+        out["bit_stream"] = ec.flush_encoder()
+        return out
+
+    @frame_encoder
+    def encode_frame(self, x, dpb, mv_y_q_scale, y_q_scale, frame_idx=None):
+        """Encoder only: {"payload": the bytes of the reference-format frame
+        file (pack_p), "dpb": the encoder's own reconstruction, "bit",
+        "precision_fallback"} (layers.frame_encoder).  ``frame_idx`` is
+        unused (HEM's P codec does not depend on it)."""
+        mv_y_q_scale, mv_y_q_index = get_rounded_q(mv_y_q_scale)
+        y_q_scale, y_q_index = get_rounded_q(y_q_scale)
+        enc = self.compress(x, dpb, mv_y_q_scale, y_q_scale, recon=True)
+        payload = pack_p(enc["bit_stream"], mv_y_q_index, y_q_index)
+        return {"payload": payload, "dpb": enc["dpb"], "bit": len(payload) * 8}
+
+    @frame_decoder
+    def decode_frame(self, payload, dpb, height, width):
+        """Decoder only: {"dpb"} from a frame's bytes and the decoder's own
+        dpb (layers.frame_decoder: ``fallback`` selects the fp32 twin)."""
+        mv_y_q_index, y_q_index, string = unpack_p(payload)
+        return self.decompress(dpb, string, height, width, mv_y_q_index / 100, y_q_index / 100)
 
     def decompress(self, dpb, string, height, width, mv_y_q_scale, y_q_scale):
         """video_model.py:332-375."""

@@ -130,6 +130,9 @@ HIP_SYMBOLS = [
     ("dcvc_avgpool2_f64", _i, [_vp, _i, _i, _vp, _vp]),
     ("dcvc_yuv_planes_f64_f32", _i, [_T, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     ("dcvc_rgb_planes_f64_f32", _i, [_T, _vp, _i, _i, _vp, _vp, _vp]),
+    ("dcvc_digest_workspace", ctypes.c_int64, []),
+    ("dcvc_digest_threads", _i, []),
+    ("dcvc_digest", _i, [_T, ctypes.c_uint64, _vp, _vp, _vp]),
     ("dcvc_debug_poison_lds", _i, [_i, _i, _vp]),
     ("dcvc_debug_poison_vgpr", _i, [_i, _vp]),
 ]
@@ -951,3 +954,35 @@ def se_apply(a, x, scale, y=None):
 def fill(y, value=0.0):
     check(lib().dcvc_fill(y.c(), float(value), stream()), "fill")
     return y
+
+
+# ---- DPB digest (digest.hip)
+def digest_workspace(device):
+    """Device scratch of one dcvc_digest call (this host thread's, per device:
+    calls on one stream are ordered, so back-to-back digests share it)."""
+    d = getattr(_tls, "digest_ws", None)
+    if d is None:
+        d = _tls.digest_ws = {}
+    ws = d.get(device)
+    if ws is None:
+        ws = d[device] = torch.empty(int(lib().dcvc_digest_workspace()) // 8, dtype=torch.int64, device=device)
+    return ws
+
+
+def digest_threads():
+    """Threads of the digest kernel's full grid on the current device."""
+    return int(check(lib().dcvc_digest_threads(), "digest_threads"))
+
+
+def digest(act, seed, out, workspace=None):
+    """Fold the digest of ``act`` (any F32 / BF16 Act, channel windows
+    included) under ``seed`` into ``out``, two device 64-bit words (int64 or
+    uint64 storage): out[0] += S, out[1] ^= X (dcvc_digest).  Asynchronous on
+    the current stream; ``out`` must start from known words (zeros)."""
+    assert out.numel() >= 2 and out.element_size() == 8 and out.is_contiguous() and out.device == act.buf.device
+    ws = workspace if workspace is not None else digest_workspace(act.buf.device)
+    status = lib().dcvc_digest(act.c(), int(seed) & 0xFFFFFFFFFFFFFFFF, ws.data_ptr(), out.data_ptr(), stream())
+    if status == -3:
+        raise NativeError("digest: unsupported dtype")
+    check(status, "digest")
+    return out

@@ -130,6 +130,84 @@ def split_guarded(fn):
     return run
 
 
+class StreamMismatchError(RuntimeError):
+    """A stand-alone decoder met something the encoder of the stream cannot
+    have produced: a split-precision decode left the split's range on a frame
+    the encoder coded in split precision (it ran every kernel the decoder
+    runs, on the same values, without tripping the guard)."""
+
+
+def frame_encoder(fn):
+    """``encode_frame`` of a codec: ``fn`` is the unguarded body
+    (``compress(recon=True)`` and the frame's reference-format bytes).  In
+    Precision.split() the fp16 range guard is armed for the frame and checked
+    once, after the encoder-side reconstruction; a frame that trips it is
+    coded again, whole, by the fp32 twin (the policy of ``split_guarded``) and
+    reported as ``precision_fallback: "parity"``, which the caller stores with
+    the frame so that a stand-alone decoder takes the twin as well.  The guard
+    is disarmed on the way out whatever happens."""
+    import functools
+
+    @functools.wraps(fn)
+    def run(self, *args, **kw):
+        if self.prec.feat_compute != F16X3:
+            out = fn(self, *args, **kw)
+            out["precision_fallback"] = None
+            return out
+        ec = self.entropy_coder
+        trace = getattr(ec, "trace", None) if ec is not None else None
+        n0 = len(trace) if trace is not None else 0
+        K.split_guard_arm(self.dev)
+        self._guard_on = True
+        try:
+            out = fn(self, *args, **kw)
+            K.split_guard_check(f"{type(self).__name__}.encode_frame")
+            out["precision_fallback"] = None
+            return out
+        except K.SplitRangeError as e:
+            reason = str(e)
+        finally:
+            self._guard_on = False
+            K.split_guard_disarm()
+        if trace is not None:
+            del trace[n0:]
+        self.fallbacks = getattr(self, "fallbacks", 0) + 1
+        out = parity_twin(self).encode_frame(*args, **kw)
+        out["precision_fallback"] = "parity"
+        out["precision_fallback_reason"] = reason
+        return out
+    return run
+
+
+def frame_decoder(fn):
+    """``decode_frame`` of a codec: ``fn(codec, payload, dpb, height, width)``
+    is the unguarded body (unpack + ``decompress``).  ``fallback`` says the
+    frame was coded by the fp32 twin, which then decodes it.  A split decode
+    that trips the range guard is an error (StreamMismatchError), never a
+    silent change of precision."""
+    import functools
+
+    @functools.wraps(fn)
+    def run(self, payload, dpb=None, height=None, width=None, fallback=False):
+        if self.prec.feat_compute != F16X3:
+            return fn(self, payload, dpb, height, width)
+        if fallback:
+            return fn(parity_twin(self), payload, dpb, height, width)
+        K.split_guard_arm(self.dev)
+        self._guard_on = True
+        try:
+            out = fn(self, payload, dpb, height, width)
+            K.split_guard_check(f"{type(self).__name__}.decode_frame")
+            return out
+        except K.SplitRangeError as e:
+            raise StreamMismatchError(f"the stream says this frame was coded in split precision, but decoding it "
+                                      f"left the split's range: {e}") from None
+        finally:
+            self._guard_on = False
+            K.split_guard_disarm()
+    return run
+
+
 class Ctx:
     """Builds layers from a state_dict on one device under one precision."""
 

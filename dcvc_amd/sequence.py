@@ -1,0 +1,356 @@
+"""One coded video in one file, written by an encoder that never decodes and
+read by a decoder that never encodes (INTEGRATION.md "Sequence file").
+
+``SequenceWriter`` / ``SequenceReader`` are the host side (no GPU): a header
+that says which codec, format and precision wrote the file, then one record
+per frame with its type, flags, the DPB digest and the unmodified
+reference-format frame bytes (``stream_helper.pack_i`` / ``pack_p``).
+
+``SequenceEncoder`` / ``SequenceDecoder`` drive the codecs' ``encode_frame`` /
+``decode_frame``.  Each keeps its own decoded picture buffer from frame to
+frame; the encoder stores a digest of it per frame (``hip.digest`` folded over
+the DPB tensors) and the decoder compares its own, so any difference between
+the two sides stops the decode at the first frame it touches instead of
+drifting through the GOP.
+
+``python -m dcvc_amd.sequence encode|decode ...`` wraps
+``harness.encode_video`` / ``decode_video``.
+"""
+import struct
+
+import torch
+
+MAGIC = b"DCVCSEQ1"
+CODECS = ("DC", "HEM")
+FORMATS = ("rgb", "yuv420")
+NOT_CLOSED = 0xFFFFFFFF
+FLAG_TWIN, FLAG_DIGEST = 1, 2
+_HEADER = struct.Struct("<8sBB16sHIII")     # magic, codec, format, precision, reserved, width, height, frames
+_RECORD = struct.Struct("<BBHIQQ")          # type, flags, reserved, payload length, digest S, digest X
+_COUNT_AT = _HEADER.size - 4
+# seeds of the frame digest, by DPB entry (an I frame: x_hat under seed 1)
+DIGEST_SEEDS = (("ref_frame", 1), ("ref_feature", 2), ("ref_mv_feature", 3), ("ref_y", 4), ("ref_mv_y", 5))
+
+
+class SequenceFormatError(ValueError):
+    """Not a sequence file, or one that is truncated or was never closed."""
+
+
+class DigestMismatch(RuntimeError):
+    """The decoder's DPB after a frame is not the encoder's."""
+
+    def __init__(self, frame_idx, stored, computed):
+        self.frame_idx, self.stored, self.computed = frame_idx, tuple(stored), tuple(computed)
+        super().__init__(f"frame {frame_idx}: the stream stores DPB digest ({stored[0]:#018x}, {stored[1]:#018x}), "
+                         f"this decoder computed ({computed[0]:#018x}, {computed[1]:#018x})")
+
+
+# ---------------------------------------------------------------- the file
+class SequenceWriter:
+    def __init__(self, path, codec, fmt, precision, width, height):
+        if codec not in CODECS or fmt not in FORMATS:
+            raise ValueError(f"unknown codec / format {codec!r} / {fmt!r}")
+        name = precision.encode("ascii")
+        if not 0 < len(name) <= 16:
+            raise ValueError(f"precision name {precision!r} does not fit 16 bytes")
+        self.frames = 0
+        self.file = open(path, "wb")  # noqa: SIM115 (closed in close())
+        self.file.write(_HEADER.pack(MAGIC, CODECS.index(codec), FORMATS.index(fmt), name, 0, width, height,
+                                     NOT_CLOSED))
+
+    def write(self, frame_type, payload, twin=False, digest=None):
+        if frame_type not in ("I", "P"):
+            raise ValueError(f"unknown frame type {frame_type!r}")
+        flags = (FLAG_TWIN if twin else 0) | (FLAG_DIGEST if digest is not None else 0)
+        s, x = digest if digest is not None else (0, 0)
+        self.file.write(_RECORD.pack("IP".index(frame_type), flags, 0, len(payload), s, x))
+        self.file.write(payload)
+        self.frames += 1
+
+    def close(self):
+        """Patch the frame count in; a file without it counts as unfinished."""
+        if self.file is None:
+            return
+        self.file.seek(_COUNT_AT)
+        self.file.write(struct.pack("<I", self.frames))
+        self.file.close()
+        self.file = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class SequenceReader:
+    """Header fields as attributes (codec, format, precision, width, height,
+    frames); iterating yields {"type", "twin", "digest" (or None), "payload"}."""
+
+    def __init__(self, path):
+        self.path = path
+        self.file = open(path, "rb")  # noqa: SIM115 (closed in close())
+        head = self.file.read(_HEADER.size)
+        if len(head) < _HEADER.size or head[:8] != MAGIC:
+            self.close()
+            raise SequenceFormatError(f"{path}: not a {MAGIC.decode()} sequence file")
+        _, codec, fmt, name, _, self.width, self.height, self.frames = _HEADER.unpack(head)
+        if codec >= len(CODECS) or fmt >= len(FORMATS):
+            self.close()
+            raise SequenceFormatError(f"{path}: unknown codec / format code {codec} / {fmt}")
+        self.codec, self.format = CODECS[codec], FORMATS[fmt]
+        self.precision = name.rstrip(b"\0").decode("ascii")
+        if self.frames == NOT_CLOSED:
+            self.close()
+            raise SequenceFormatError(f"{path}: the file was not closed by its encoder (no frame count)")
+
+    def __iter__(self):
+        for i in range(self.frames):
+            head = self.file.read(_RECORD.size)
+            if len(head) < _RECORD.size:
+                raise SequenceFormatError(f"{self.path}: truncated in the record header of frame {i}")
+            ftype, flags, _, n, s, x = _RECORD.unpack(head)
+            if ftype > 1:
+                raise SequenceFormatError(f"{self.path}: frame {i} has unknown type {ftype}")
+            payload = self.file.read(n)
+            if len(payload) < n:
+                raise SequenceFormatError(f"{self.path}: truncated in the payload of frame {i} "
+                                          f"({len(payload)} of {n} bytes)")
+            yield {"type": "IP"[ftype], "twin": bool(flags & FLAG_TWIN),
+                   "digest": (s, x) if flags & FLAG_DIGEST else None, "payload": payload}
+
+    def close(self):
+        if self.file is not None:
+            self.file.close()
+            self.file = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+# -------------------------------------------------------------- the drivers
+def codec_of(net):
+    return "HEM" if type(net).__module__.startswith("dcvc_amd.hem") else "DC"
+
+
+def _describe(i_net, p_net):
+    """(codec, format, precision name) of a pair of nets.  The format is the
+    nets' ``codec_format`` attribute ("rgb" unless the caller, who knows which
+    checkpoint they hold, set "yuv420")."""
+    codec = codec_of(i_net)
+    if codec_of(p_net) != codec:
+        raise ValueError("the I and the P codec are not of one family (DC / HEM)")
+    fmt = getattr(i_net, "codec_format", "rgb")
+    if getattr(p_net, "codec_format", "rgb") != fmt or fmt not in FORMATS:
+        raise ValueError("the I and the P codec do not carry one codec_format (rgb / yuv420)")
+    if i_net.prec.name != p_net.prec.name:
+        raise ValueError(f"the I codec runs in {i_net.prec.name} precision, the P codec in {p_net.prec.name}")
+    return codec, fmt, i_net.prec.name
+
+
+class FrameDigest:
+    """The frame digest: ``hip.digest`` folded over the DPB entries in the
+    order and under the seeds of DIGEST_SEEDS, all on the current stream; one
+    16-byte transfer (which waits for them) returns the two words."""
+
+    def __init__(self, device):
+        self.out = torch.zeros(2, dtype=torch.int64, device=device)
+
+    def __call__(self, dpb):
+        from . import hip as K
+        from .dc.video_model import as_act
+        self.out.zero_()
+        for name, seed in DIGEST_SEEDS:
+            t = dpb.get(name)
+            if t is None:
+                continue
+            if isinstance(t, torch.Tensor) and t.dim() == 3:      # an (H, W, C) copy of an entry
+                t = K.Act(t.contiguous())
+            K.digest(as_act(t), seed, self.out)
+        s, x = self.out.cpu().tolist()
+        return s & 0xFFFFFFFFFFFFFFFF, x & 0xFFFFFFFFFFFFFFFF
+
+
+def _i_dpb(codec, x_hat):
+    dpb = {"ref_frame": x_hat, "ref_feature": None, "ref_y": None, "ref_mv_y": None}
+    if codec == "DC":
+        dpb["ref_mv_feature"] = None
+    return dpb
+
+
+class SequenceEncoder:
+    """Encoder only.  ``encode(x)`` takes the padded codec input of one frame
+    (what ``FrameStage.load`` produces), codes it against the encoder's own
+    DPB, appends the record and returns the codec's ``encode_frame`` dict plus
+    "type", "recon" (the (1, 3, H, W) reconstruction) and "digest".  The I/P
+    schedule, the P codec's q and ``frame_idx`` are those of ``run_test`` /
+    ``run_test_hem``: DC passes (q_in_ckpt, q_index) to both codecs and
+    ``frame_idx % 4``; HEM passes i_frame_q_scale and the two P scales."""
+
+    def __init__(self, i_net, p_net, path, width, height, gop_size, q_in_ckpt=False, q_index=None,
+                 i_frame_q_scale=None, p_frame_mv_y_q_scale=None, p_frame_y_q_scale=None, yuv420=False, digest=True):
+        self.codec, fmt, prec = _describe(i_net, p_net)
+        if fmt != FORMATS[int(bool(yuv420))]:
+            raise ValueError(f"the nets carry codec_format {fmt!r}, the caller asks for {FORMATS[int(bool(yuv420))]!r}")
+        if self.codec == "DC" and q_index is None:
+            raise ValueError("the DC codecs need q_index")
+        if self.codec == "HEM" and None in (i_frame_q_scale, p_frame_mv_y_q_scale, p_frame_y_q_scale):
+            raise ValueError("the HEM codecs need i_frame_q_scale, p_frame_mv_y_q_scale and p_frame_y_q_scale")
+        self.i_net, self.p_net = i_net, p_net
+        self.width, self.height, self.gop_size = width, height, gop_size
+        self.q = (q_in_ckpt, q_index) if self.codec == "DC" else (i_frame_q_scale, p_frame_mv_y_q_scale,
+                                                                  p_frame_y_q_scale)
+        self.digest = FrameDigest(i_net.dev) if digest else None
+        self.writer = SequenceWriter(path, self.codec, fmt, prec, width, height)
+        self.dpb = None
+        self.n = 0
+
+    def encode(self, x):
+        frame_idx = self.n
+        with torch.no_grad():
+            if frame_idx % self.gop_size == 0:
+                if self.codec == "DC":
+                    out = self.i_net.encode_frame(x, self.q[0], self.q[1], self.height, self.width)
+                else:
+                    out = self.i_net.encode_frame(x, self.q[0], self.height, self.width)
+                self.dpb = _i_dpb(self.codec, out["x_hat"])
+                ftype = "I"
+            else:
+                if self.codec == "DC":
+                    out = self.p_net.encode_frame(x, self.dpb, self.q[0], self.q[1], frame_idx % 4)
+                else:
+                    out = self.p_net.encode_frame(x, self.dpb, self.q[1], self.q[2])
+                self.dpb = out["dpb"]
+                ftype = "P"
+            dig = self.digest(self.dpb) if self.digest is not None else None
+        self.writer.write(ftype, out["payload"], twin=out["precision_fallback"] == "parity", digest=dig)
+        self.n += 1
+        return dict(out, type=ftype, recon=self.dpb["ref_frame"], digest=dig)
+
+    def close(self):
+        self.writer.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class SequenceDecoder:
+    """Decoder only: iterating yields, per frame, {"type", "x_hat" (the
+    (1, 3, H, W) decoded frame), "dpb", "bit"}.  Raises ValueError when the
+    nets are not what the header says wrote the file, DigestMismatch when a
+    stored digest is not the digest of this decoder's DPB, and
+    SequenceFormatError on a truncated or unclosed file."""
+
+    def __init__(self, i_net, p_net, path):
+        mine = _describe(i_net, p_net)
+        self.reader = SequenceReader(path)
+        r = self.reader
+        theirs = (r.codec, r.format, r.precision)
+        if mine != theirs:
+            r.close()
+            raise ValueError(f"{path} was written by {theirs} codecs (codec, format, precision); these are {mine}")
+        self.i_net, self.p_net, self.codec = i_net, p_net, r.codec
+        self.width, self.height, self.frames = r.width, r.height, r.frames
+        self.digest = FrameDigest(i_net.dev)
+
+    def __iter__(self):
+        dpb = None
+        for idx, rec in enumerate(self.reader):
+            with torch.no_grad():
+                if rec["type"] == "I":
+                    x_hat = self.i_net.decode_frame(rec["payload"], None, self.height, self.width,
+                                                    fallback=rec["twin"])["x_hat"]
+                    dpb = _i_dpb(self.codec, x_hat)
+                else:
+                    if dpb is None:
+                        raise SequenceFormatError(f"{self.reader.path}: frame {idx} is a P frame with no frame before it")
+                    dpb = self.p_net.decode_frame(rec["payload"], dpb, self.height, self.width,
+                                                  fallback=rec["twin"])["dpb"]
+                if rec["digest"] is not None:
+                    got = self.digest(dpb)
+                    if got != rec["digest"]:
+                        raise DigestMismatch(idx, rec["digest"], got)
+            yield {"type": rec["type"], "x_hat": dpb["ref_frame"], "dpb": dpb, "bit": len(rec["payload"]) * 8}
+
+    def close(self):
+        self.reader.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+# ------------------------------------------------------------ command line
+def _load_nets(a):
+    from .layers import Precision
+    from .stream_helper import get_state_dict
+    if a.codec == "hem":
+        from .hem import IntraNoAR, DMC
+    else:
+        from .dc import IntraNoAR, DMC
+    prec = getattr(Precision, a.precision)()
+    i_net = IntraNoAR(precision=prec).load_state_dict(get_state_dict(a.i_frame_model_path))
+    p_net = DMC(precision=prec).load_state_dict(get_state_dict(a.p_frame_model_path))
+    for net in (i_net, p_net):
+        net.update(force=True)
+        net.codec_format = FORMATS[int(a.yuv420)]
+    return i_net, p_net
+
+
+def main(argv=None):
+    import argparse
+    import json
+    from . import harness
+    ap = argparse.ArgumentParser(prog="python -m dcvc_amd.sequence", description=__doc__.split("\n\n")[0])
+    ap.add_argument("mode", choices=("encode", "decode"))
+    ap.add_argument("--codec", choices=("dc", "hem"), default="dc")
+    ap.add_argument("--precision", choices=("split", "parity"), default="split")
+    ap.add_argument("--i_frame_model_path", required=True)
+    ap.add_argument("--p_frame_model_path", required=True)
+    ap.add_argument("--yuv420", action="store_true", help="the checkpoints are YUV420 models (dist_in_yuv420)")
+    ap.add_argument("--seq_path", required=True, help="the sequence file to write (encode) or read (decode)")
+    ap.add_argument("--src_type", choices=("png", "yuv420"), default=None)
+    ap.add_argument("--src_path")
+    ap.add_argument("--src_width", type=int)
+    ap.add_argument("--src_height", type=int)
+    ap.add_argument("--frame_num", type=int)
+    ap.add_argument("--gop_size", type=int, default=32)
+    ap.add_argument("--q_in_ckpt", action="store_true")
+    ap.add_argument("--q_index", type=int, default=None)
+    ap.add_argument("--i_frame_q_scale", type=float, default=None)
+    ap.add_argument("--p_frame_mv_y_q_scale", type=float, default=None)
+    ap.add_argument("--p_frame_y_q_scale", type=float, default=None)
+    ap.add_argument("--no_digest", action="store_true")
+    ap.add_argument("--recon_path", default=None, help="decode: folder for the decoded frames")
+    a = ap.parse_args(argv)
+    i_net, p_net = _load_nets(a)
+    args = {"seq_path": a.seq_path, "dist_in_yuv420": a.yuv420, "digest": not a.no_digest}
+    if a.src_type is not None:
+        args["src_type"] = a.src_type
+    if a.mode == "encode":
+        args.update(src_path=a.src_path, src_width=a.src_width, src_height=a.src_height, frame_num=a.frame_num,
+                    gop_size=a.gop_size, q_in_ckpt=a.q_in_ckpt, i_frame_q_index=a.q_index,
+                    i_frame_q_scale=a.i_frame_q_scale, p_frame_mv_y_q_scale=a.p_frame_mv_y_q_scale,
+                    p_frame_y_q_scale=a.p_frame_y_q_scale, verbose=1)
+        out = harness.encode_video(i_net, p_net, args)
+    else:
+        if a.recon_path is not None:
+            args.update(save_decoded_frame=True, recon_path=a.recon_path, decoded_frame_folder=a.recon_path)
+        out = harness.decode_video(i_net, p_net, args)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -482,6 +482,31 @@ int dcvc_rgb_planes_f64_f32(dcvc_tensor x_hat, const float *src, int h, int w,
                             double *src_planes, double *rec_planes,
                             void *stream);
 
+/*
+ * Order-independent 128-bit digest of a view (F32 or BF16, any channel window;
+ * DCVC_HIP_EUNSUPPORTED for another dtype, DCVC_HIP_EINVAL when H*W*C >= 2^32).
+ * Per element, with n = (y*W + x)*C + c the index inside the VIEW (whatever the
+ * buffer's pitch and channel offset) and b its bit pattern (32 bits for fp32,
+ * 16 bits zero-extended for bf16; -0.0 counted as +0.0, every other bit
+ * counts, NaN payloads included):
+ *   h = mix64(((uint64)b << 32 | (uint32)n) + seed * 0x9E3779B97F4A7C15)
+ *   mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *             z *= 0x94D049BB133111EB; z ^= z >> 31     (all mod 2^64)
+ * and S = sum of h mod 2^64, X = xor of h.  The call FOLDS into out (two
+ * device uint64): out[0] += S, out[1] ^= X, so several tensors are digested
+ * back to back on one stream into one pair of words.  Add and xor are
+ * associative: the result does not depend on the reduction order.  No atomics.
+ * workspace: dcvc_digest_workspace() bytes of device scratch, 8-byte aligned.
+ * dcvc_digest_threads(): the thread count of the main kernel's full grid on
+ * the current device (4 blocks of 256 per CU); the 16-byte path covers two
+ * times that many 16-byte items per pass of its loop, the scalar path one
+ * element per thread and pass.
+ */
+int64_t dcvc_digest_workspace(void);
+int dcvc_digest_threads(void);
+int dcvc_digest(dcvc_tensor t, uint64_t seed, uint64_t *workspace,
+                uint64_t *out, void *stream);
+
 /* Debug aid: fill the LDS of `blocks` workgroups with all-ones bytes (NaN in
  * bf16 / fp32), to expose kernels that read LDS they never wrote
  * (scripts/lds_poison_check.py).  Not used by the codec. */
