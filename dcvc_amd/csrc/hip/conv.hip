@@ -18,6 +18,8 @@
 // them (see dcvc_conv_args in include/dcvc_hip.h).
 #include "common.h"
 #include "epilogue.h"
+#include "launch.h"
+#include "options.h"
 #include "split.h"
 
 #include <cmath>
@@ -425,8 +427,8 @@ int launch(const ConvP &p0, hipStream_t st) {
 // Tile choice: BN covers Cout in the fewest n-tiles (max 128); TH shrinks
 // from 16 (8 when strided) to 4 until the grid has >= 1024 workgroups, so
 // the small latent-resolution GEMMs still fill the 256 CUs.
-int g_force_th = 0;  // dcvc_set_option("conv_th", 4 | 8 | 16): A/B of the tile height (7x7 convs)
-int g_force_bn = 0;  // dcvc_set_option("conv_bn", 16..128): A/B of the n-tile width (7x7 convs)
+DCVC_OPTION("conv_th", g_force_th, 0);  // 4 | 8 | 16: A/B of the tile height (7x7 convs)
+DCVC_OPTION("conv_bn", g_force_bn, 0);  // 16..128: A/B of the n-tile width (7x7 convs)
 
 template <typename TIN, typename TOUT, bool F32, int BN>
 int pick_th(const ConvP &p, hipStream_t st) {
@@ -480,8 +482,8 @@ int pick_bn(const ConvP &p, hipStream_t st) {
   }
 }
 
-int g_use_gemm = 1;   // dcvc_set_option("gemm1x1", 0) routes 1x1 convs to the generic kernel
-int g_use_conv3 = 1;  // dcvc_set_option("conv3x3", 0) routes 3x3 s1 convs to the generic kernel
+DCVC_OPTION("gemm1x1", g_use_gemm, 1);   // 0 routes 1x1 stride-1 bf16 convs to the generic kernel (1: the double-buffered GEMM)
+DCVC_OPTION("conv3x3", g_use_conv3, 1);  // 0 routes 3x3 stride-1 bf16 convs to the generic kernel (1: the fixed-geometry kernels)
 
 bool valid_view(const dcvc_tensor &t) {
   return t.ptr && t.H > 0 && t.W > 0 && t.C > 0 && t.coff >= 0 && t.coff + t.C <= t.cstride &&
@@ -498,17 +500,14 @@ bool valid_view(const dcvc_tensor &t) {
 // hi) * 2^11): w = hi + 2^-11 lo to ~2^-22.
 static int64_t pack_f16x3(const float *w, int cout, int cin, int kh, int kw, uint16_t *out) {
   const int kt = kh * kw;
-  const int nch = (cin + 31) / 32;
-  const int vcl = cin - 32 * (nch - 1);
-  const int tpkl = vcl <= 8 ? 4 : vcl <= 16 ? 2 : 1;
-  const int64_t full = (int64_t)2 * kt * cout * 32;
-  const int64_t total = (int64_t)(nch - 1) * full + (int64_t)2 * ((kt + tpkl - 1) / tpkl) * cout * 32;
-  if (!out) return total;
-  for (int c = 0; c < nch; ++c) {
-    const int tpk = c == nch - 1 ? tpkl : 1;
+  const SplitWLayout l = split_wlayout(cin, cout, kh, kw);
+  if (!out) return l.halves;
+  for (int c = 0; c < l.nch; ++c) {
+    const bool last = c == l.nch - 1;
+    const int tpk = last ? l.tpk_last : 1;
     const int spt = 4 / tpk;
-    const int rows = (kt + tpk - 1) / tpk;
-    uint16_t *hi = out + (int64_t)c * full;
+    const int rows = last ? l.rows_last : kt;
+    uint16_t *hi = out + (int64_t)c * l.wchunk;
     uint16_t *lo = hi + (int64_t)rows * cout * 32;
     for (int r = 0; r < rows; ++r)
       for (int n = 0; n < cout; ++n)
@@ -522,7 +521,7 @@ static int64_t pack_f16x3(const float *w, int cout, int cin, int kh, int kw, uin
           host_split(v, hi[o], lo[o]);
         }
   }
-  return total;
+  return l.halves;
 }
 
 extern "C" int64_t dcvc_conv_pack_weights(const float *w, int cout, int cin, int kh, int kw,
@@ -558,51 +557,16 @@ extern "C" int64_t dcvc_conv_pack_weights(const float *w, int cout, int cin, int
 
 extern "C" int dcvc_internal_gemm1x1(const dcvc_conv_args *a, void *stream);
 extern "C" int dcvc_internal_gemm1x1_f32(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_gemm1x1_f32_enable(int v);
-extern "C" void dcvc_internal_gemm3x3_f32_enable(int v);
-extern "C" void dcvc_internal_gemm1x1_f32_cfg(int v);
-extern "C" void dcvc_internal_gemm1x1_f32_upfront(int v);
-extern "C" void dcvc_internal_gemm1x1_f32_direct(int v);
 extern "C" int dcvc_internal_conv3x3(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_conv3x3_resident(int v);
-extern "C" void dcvc_internal_conv3p_enable(int v);
-extern "C" void dcvc_internal_dcbp_enable(int v);
-extern "C" void dcvc_internal_dcbs_enable(int v);
 extern "C" int dcvc_internal_conv7s(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_conv7s_enable(int v);
 extern "C" int dcvc_internal_conv7w(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_conv7w_enable(int v);
 extern "C" int dcvc_internal_conv3s2(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_conv3s2_enable(int v);
-extern "C" void dcvc_internal_conv3p_occupancy(int v);
-extern "C" void dcvc_internal_conv3p_mode(int v);
-extern "C" void dcvc_internal_conv3p_rows4(int v);
-extern "C" void dcvc_internal_gemm1x1_bm(int v);
 extern "C" int dcvc_internal_sconv(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_sconv_occupancy(int v);
-extern "C" void dcvc_internal_sconv_waves(int v);
-extern "C" void dcvc_internal_sconv_resident(int v);
-extern "C" void dcvc_internal_sconv_res_waves(int v);
-extern "C" void dcvc_internal_sgemm_cfg(int v);
-extern "C" void dcvc_internal_sgemm_pd(int v);
-extern "C" void dcvc_internal_sgemm_gate(int v);
-extern "C" int dcvc_internal_set_option_split(const char *name, int value);
 extern "C" int dcvc_internal_xconv(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_xconv_enable(int v);
 extern "C" int dcvc_internal_wconv(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_wconv_enable(int v);
 extern "C" int dcvc_internal_dconv(const dcvc_conv_args *a, void *stream);
 extern "C" int dcvc_internal_tconv(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_tconv_enable(int v);
 extern "C" int dcvc_internal_nconv(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_nconv_enable(int v);
-extern "C" void dcvc_internal_sffn128(int v);
-extern "C" void dcvc_internal_dconv_enable(int v);
-extern "C" void dcvc_internal_dconv_1x1(int v);
-extern "C" void dcvc_internal_dconv_xcd(int v);
-extern "C" void dcvc_internal_dconv_gate(int v);
-extern "C" void dcvc_internal_dconv_s2blocks(int v);
-extern "C" void dcvc_internal_dconv_bn128(int v);
 
 // fp16 range guard of the split kernels (split.h SplitRange): one flag per
 // calling host thread (concurrent GOP lanes each launch from their own thread
@@ -723,161 +687,4 @@ extern "C" int dcvc_conv2d(const dcvc_conv_args *a, void *stream) {
   if (xin32 && !yout32) return pick_bn<float, uint16_t, false>(p, st);
   if (!xin32 && yout32) return pick_bn<uint16_t, float, false>(p, st);
   return pick_bn<uint16_t, uint16_t, false>(p, st);
-}
-
-extern "C" int dcvc_set_option(const char *name, int value) {
-  if (!name) return DCVC_HIP_EINVAL;
-  if (std::strcmp(name, "gemm1x1") == 0) {
-    g_use_gemm = value;
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "gemm1x1_f32") == 0) {
-    dcvc_internal_gemm1x1_f32_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "gemm3x3_f32") == 0) {
-    dcvc_internal_gemm3x3_f32_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "gemm1x1_f32_cfg") == 0) {
-    dcvc_internal_gemm1x1_f32_cfg(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "gemm1x1_f32_upfront") == 0) {
-    dcvc_internal_gemm1x1_f32_upfront(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "gemm1x1_f32_direct") == 0) {
-    dcvc_internal_gemm1x1_f32_direct(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv3x3") == 0) {
-    g_use_conv3 = value;
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "dcb_persistent") == 0) {
-    dcvc_internal_dcbp_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv3x3_s2") == 0) {
-    dcvc_internal_conv3s2_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv7_wide_cin") == 0) {
-    dcvc_internal_conv7w_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv7_small_cin") == 0) {
-    dcvc_internal_conv7s_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "dcb_stream") == 0) {
-    dcvc_internal_dcbs_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv3x3_persistent") == 0) {
-    dcvc_internal_conv3p_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv3x3_resident") == 0) {
-    dcvc_internal_conv3x3_resident(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv_th") == 0) {
-    g_force_th = value;
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv_bn") == 0) {
-    g_force_bn = value;
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "gemm1x1_bm") == 0) {
-    dcvc_internal_gemm1x1_bm(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv3x3_occupancy") == 0) {
-    dcvc_internal_conv3p_occupancy(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv3x3_epilogue") == 0) {
-    dcvc_internal_conv3p_mode(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "sconv_res_waves") == 0) {
-    dcvc_internal_sconv_res_waves(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "sgemm_pd") == 0) {
-    dcvc_internal_sgemm_pd(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "sgemm_gate") == 0) {
-    dcvc_internal_sgemm_gate(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "sgemm") == 0) {
-    dcvc_internal_sgemm_cfg(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "sconv_resident") == 0) {
-    dcvc_internal_sconv_resident(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "sconv_waves") == 0) {
-    dcvc_internal_sconv_waves(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "sconv_occupancy") == 0) {
-    dcvc_internal_sconv_occupancy(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "xconv") == 0) {
-    dcvc_internal_xconv_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "wconv") == 0) {
-    dcvc_internal_wconv_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "dconv") == 0) {
-    dcvc_internal_dconv_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "dconv_1x1") == 0) {
-    dcvc_internal_dconv_1x1(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "sffn128") == 0) {
-    dcvc_internal_sffn128(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "nconv") == 0) {
-    dcvc_internal_nconv_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "tconv") == 0) {
-    dcvc_internal_tconv_enable(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "dconv_xcd") == 0) {
-    dcvc_internal_dconv_xcd(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "dconv_gate") == 0) {
-    dcvc_internal_dconv_gate(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "dconv_s2blocks") == 0) {
-    dcvc_internal_dconv_s2blocks(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "dconv_bn128") == 0) {
-    dcvc_internal_dconv_bn128(value);
-    return DCVC_HIP_OK;
-  }
-  if (std::strcmp(name, "conv3x3_rows4") == 0) {
-    dcvc_internal_conv3p_rows4(value);
-    return DCVC_HIP_OK;
-  }
-  return dcvc_internal_set_option_split(name, value);   // the split-precision kernels' options (xconv.hip)
 }

@@ -20,6 +20,8 @@
 //     whole-line stores) through an fp32 tile that reuses the image.
 #include "common.h"
 #include "epilogue.h"
+#include "launch.h"
+#include "options.h"
 
 namespace {
 
@@ -183,8 +185,7 @@ __global__ void __launch_bounds__(NTHR) conv3s2_kernel(S2 p) {
   }
 }
 
-int g_cus = 0;
-int g_enabled = 1;
+DCVC_OPTION("conv3x3_s2", g_enabled, 1);   // 0: stride-2 3x3 bf16 convs to the generic kernel
 
 template <int BN, typename TOUT>
 int launch(S2 p, hipStream_t st) {
@@ -194,15 +195,10 @@ int launch(S2 p, hipStream_t st) {
   p.tiles_y = (p.Ho + TH - 1) / TH;
   p.nblk_n = (p.cout + BN - 1) / BN;
   const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-      return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
-  if (ntiles < 2LL * g_cus) return DCVC_HIP_EUNSUPPORTED;  // small maps: the per-tile kernel
-  const int per_n = g_cus / p.nblk_n;
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
+  if (ntiles < 2LL * cus) return DCVC_HIP_EUNSUPPORTED;  // small maps: the per-tile kernel
+  const int per_n = cus / p.nblk_n;
   const int G = per_n * p.nblk_n;
   auto kern = conv3s2_kernel<BN, TOUT>;
   dcvc_note_kernel("conv3s2_kernel<%d, %s>@%lld", BN, tname<TOUT>(), (long long)G * NTHR);
@@ -264,6 +260,3 @@ extern "C" int dcvc_internal_conv3s2(const dcvc_conv_args *a, void *stream) {
   if (a->cout % 48 == 0) return launch<48, uint16_t>(p, st);
   return DCVC_HIP_EUNSUPPORTED;
 }
-
-// dcvc_set_option("conv3x3_s2", 0/1) (A/B switch, via conv.hip)
-extern "C" void dcvc_internal_conv3s2_enable(int v) { g_enabled = v; }

@@ -29,6 +29,8 @@
 // fp32 rounding only (tests/test_gpu_kernels.py checks both).
 #include "common.h"
 #include "epilogue.h"
+#include "launch.h"
+#include "options.h"
 
 namespace {
 
@@ -502,8 +504,7 @@ __global__ void __launch_bounds__(256) conv3x3_res_kernel(C3 p) {
   }
 }
 
-int g_cus = 0;
-int g_resident = 1;  // 0: off, 1: measured-best shapes, 2: every fitting shape
+DCVC_OPTION("conv3x3_resident", g_resident, 1);  // persistent resident-weight variant: 0: off, 1: measured-best shapes, 2: every fitting shape
 
 template <int NCH, bool TAIL, int BN, int TH, typename TOUT>
 int launch_res(C3 p, hipStream_t st) {
@@ -516,15 +517,10 @@ int launch_res(C3 p, hipStream_t st) {
     p.nblk_n = (p.cout + BN - 1) / BN;
     const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y;
     if (ntiles <= 0) return DCVC_HIP_OK;
-    if (g_cus <= 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-        return DCVC_HIP_ELAUNCH;
-      g_cus = prop.multiProcessorCount;
-    }
+    const int cus = dcvc_cu_count();
+    if (cus <= 0) return DCVC_HIP_ELAUNCH;
     const int per_cu = (int)((160 * 1024) / lds) >= 2 ? 2 : 1;
-    int64_t G = ((int64_t)g_cus * per_cu + p.nblk_n - 1) / p.nblk_n;
+    int64_t G = ((int64_t)cus * per_cu + p.nblk_n - 1) / p.nblk_n;
     if (G > ntiles) G = ntiles;
     const bool res = p.res || p.res2;
     auto kern = res ? conv3x3_res_kernel<NCH, TAIL, BN, TH, TOUT, true>
@@ -724,6 +720,3 @@ extern "C" int dcvc_internal_conv3x3(const dcvc_conv_args *a, void *stream) {
   if (a->y.dtype == DCVC_F32) return pick_bn<float>(p, st);
   return pick_bn<uint16_t>(p, st);
 }
-
-// dcvc_set_option("conv3x3_resident", 0/1) (A/B switch, via conv.hip)
-extern "C" void dcvc_internal_conv3x3_resident(int v) { g_resident = v; }

@@ -36,6 +36,8 @@
 // as five tap pairs) and the fp32 epilogue order are those of conv3x3.hip, so
 // results are bit-identical to it (tests/test_gpu_kernels.py).
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 
 namespace {
 
@@ -529,11 +531,10 @@ __global__ void __launch_bounds__(NW * 64) conv3p_kernel(P3 p) {
   }
 }
 
-int g_cus = 0;
-int g_enabled = 1;
-int g_occ = 1;  // dcvc_set_option("conv3x3_occupancy", 2): two 8-row workgroups per CU where they fit
-int g_rows4 = 1;  // dcvc_set_option("conv3x3_rows4", 0/1): 32-row tiles where they fit (A/B; 48->48 at 1080p 176 -> 172 us, 32->32 81 -> 69)
-int g_mode = 0;  // dcvc_set_option("conv3x3_epilogue", 0/1/2, 3 = also 8-row tiles): highest epilogue mode (launch_mode)
+DCVC_OPTION("conv3x3_persistent", g_enabled, 1);   // 0: no persistent 3x3 kernel (the per-tile ones)
+DCVC_OPTION("conv3x3_occupancy", g_occ, 1);  // 2: two 8-row workgroups per CU where they fit
+DCVC_OPTION("conv3x3_rows4", g_rows4, 1);  // 0/1: 32-row tiles where they fit (A/B; 48->48 at 1080p 176 -> 172 us, 32->32 81 -> 69)
+DCVC_OPTION("conv3x3_epilogue", g_mode, 0);  // 0/1/2, 3 = also 8-row tiles: highest epilogue mode (launch_mode)
 
 template <int CIN, int BN, int NW, int RW, typename TOUT, bool SHUF, int MODE>
 int launch(P3 p, hipStream_t st, int per_cu = 1) {
@@ -545,16 +546,11 @@ int launch(P3 p, hipStream_t st, int per_cu = 1) {
     p.tiles_y = (p.H + G_::TH - 1) / G_::TH;
     p.nblk_n = (p.cout + BN - 1) / BN;
     const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y;
-    if (g_cus <= 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-        return DCVC_HIP_ELAUNCH;
-      g_cus = prop.multiProcessorCount;
-    }
+    const int cus = dcvc_cu_count();
+    if (cus <= 0) return DCVC_HIP_ELAUNCH;
     // a grid of fewer tiles than CUs is better served per tile
-    if (ntiles * p.nblk_n < g_cus) return DCVC_HIP_EUNSUPPORTED;
-    int64_t G = (int64_t)g_cus * per_cu / p.nblk_n;
+    if (ntiles * p.nblk_n < cus) return DCVC_HIP_EUNSUPPORTED;
+    int64_t G = (int64_t)cus * per_cu / p.nblk_n;
     if (G > ntiles) G = ntiles;
     if (G < 1) G = 1;
     auto kern = conv3p_kernel<CIN, BN, NW, RW, TOUT, SHUF, MODE>;
@@ -690,9 +686,3 @@ extern "C" int dcvc_internal_conv3p(const dcvc_conv_args *a, void *stream) {
     default: return DCVC_HIP_EUNSUPPORTED;
   }
 }
-
-// dcvc_set_option("conv3x3_persistent", 0/1) (A/B switch, via conv.hip)
-extern "C" void dcvc_internal_conv3p_enable(int v) { g_enabled = v; }
-extern "C" void dcvc_internal_conv3p_occupancy(int v) { g_occ = v; }
-extern "C" void dcvc_internal_conv3p_mode(int v) { g_mode = v; }
-extern "C" void dcvc_internal_conv3p_rows4(int v) { g_rows4 = v; }

@@ -19,6 +19,8 @@
 // conv.hip bit for bit (tests/test_gpu_kernels.py).
 #include "common.h"
 #include "epilogue.h"
+#include "launch.h"
+#include "options.h"
 
 namespace {
 
@@ -174,8 +176,7 @@ __global__ void __launch_bounds__(NTHR) conv7s_kernel(C7 p) {
   }
 }
 
-int g_cus = 0;
-int g_enabled = 1;
+DCVC_OPTION("conv7_small_cin", g_enabled, 1);   // 0: 8- / 16-channel 7x7 bf16 convs to the generic kernel
 
 template <int CIN, int BN, typename TOUT>
 int launch(C7 p, hipStream_t st) {
@@ -184,14 +185,9 @@ int launch(C7 p, hipStream_t st) {
   p.tiles_x = (p.W + TT - 1) / TT;
   p.tiles_y = (p.H + TT - 1) / TT;
   const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-      return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
-  const int G = ntiles < 2 * g_cus ? (int)ntiles : 2 * g_cus;
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
+  const int G = ntiles < 2 * cus ? (int)ntiles : 2 * cus;
   auto kern = conv7s_kernel<CIN, BN, TOUT>;
   dcvc_note_kernel("conv7s_kernel<%d, %d, %s>@%lld", CIN, BN, tname<TOUT>(), (long long)G * NTHR);
   if (G_::LDS > 64 * 1024) dcvc_ensure_lds(reinterpret_cast<const void *>(kern), (int)G_::LDS);
@@ -250,6 +246,3 @@ extern "C" int dcvc_internal_conv7s(const dcvc_conv_args *a, void *stream) {
   if (a->cin == 8) return y32 ? launch<8, 16, float>(p, st) : launch<8, 16, uint16_t>(p, st);
   return y32 ? launch<16, 16, float>(p, st) : launch<16, 16, uint16_t>(p, st);
 }
-
-// dcvc_set_option("conv7_small_cin", 0/1) (A/B switch, via conv.hip)
-extern "C" void dcvc_internal_conv7s_enable(int v) { g_enabled = v; }

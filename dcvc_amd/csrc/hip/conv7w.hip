@@ -19,6 +19,8 @@
 //   * the conv epilogue of epilogue.h through an fp32 tile over the image.
 #include "common.h"
 #include "epilogue.h"
+#include "launch.h"
+#include "options.h"
 
 namespace {
 
@@ -178,8 +180,7 @@ __global__ void __launch_bounds__(NTHR) conv7w_kernel(C7W p) {
   }
 }
 
-int g_cus = 0;
-int g_enabled = 1;
+DCVC_OPTION("conv7_wide_cin", g_enabled, 1);   // 0: 32- / 64-channel 7x7 bf16 convs to the generic kernel
 
 template <int CIN, int BN, typename TOUT>
 int launch(C7W p, hipStream_t st) {
@@ -189,15 +190,10 @@ int launch(C7W p, hipStream_t st) {
   p.tiles_y = (p.H + TT - 1) / TT;
   p.nblk_n = (p.cout + BN - 1) / BN;
   const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-      return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
   // one workgroup per CU over the n-blocks; small maps: one per tile
-  int per_n = g_cus / p.nblk_n;
+  int per_n = cus / p.nblk_n;
   if (per_n > ntiles) per_n = (int)ntiles;
   const int G = per_n * p.nblk_n;
   auto kern = conv7w_kernel<CIN, BN, TOUT>;
@@ -256,6 +252,3 @@ extern "C" int dcvc_internal_conv7w(const dcvc_conv_args *a, void *stream) {
   if (a->cin == 32) return a->cout > 16 ? launch<32, 32, uint16_t>(p, st) : launch<32, 16, uint16_t>(p, st);
   return launch<64, 16, uint16_t>(p, st);
 }
-
-// dcvc_set_option("conv7_wide_cin", 0/1) (A/B switch, via conv.hip)
-extern "C" void dcvc_internal_conv7w_enable(int v) { g_enabled = v; }

@@ -17,6 +17,8 @@
 // The MFMA K order and every rounding point are those of dcb.hip, so outputs
 // are bit-identical to it (tests/test_gpu_kernels.py).
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 
 namespace {
 
@@ -432,8 +434,7 @@ __global__ void __launch_bounds__(NTHR) dcbp_kernel(DcbP p) {
   }
 }
 
-int g_cus = 0;
-int g_enabled = 1;
+DCVC_OPTION("dcb_persistent", g_enabled, 1);   // 0: no persistent fused DepthConvBlock (the per-tile kernel)
 
 template <int CIN, int COUT, bool ADAPT>
 int run(DcbP p, hipStream_t st) {
@@ -444,15 +445,10 @@ int run(DcbP p, hipStream_t st) {
     p.tiles_x = (p.W + TW - 1) / TW;
     p.tiles_y = (p.H + TH - 1) / TH;
     const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y;
-    if (g_cus <= 0) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-        return DCVC_HIP_ELAUNCH;
-      g_cus = prop.multiProcessorCount;
-    }
-    if (ntiles < 2LL * g_cus) return DCVC_HIP_EUNSUPPORTED;  // small maps: per-tile kernel
-    const int G = g_cus;
+    const int cus = dcvc_cu_count();
+    if (cus <= 0) return DCVC_HIP_ELAUNCH;
+    if (ntiles < 2LL * cus) return DCVC_HIP_EUNSUPPORTED;  // small maps: per-tile kernel
+    const int G = cus;
     auto kern = dcbp_kernel<CIN, COUT, ADAPT>;
     dcvc_note_kernel("dcbp_kernel<%d, %d, %s>@%lld", CIN, COUT, bname(ADAPT), (long long)G * NTHR);
     dcvc_ensure_lds(reinterpret_cast<const void *>(kern), (int)G_::LDS);
@@ -498,6 +494,3 @@ extern "C" int dcvc_internal_dcbp(const dcvc_dcb_args *a, void *stream) {
   if (a->cin == 64 && a->cout == 64 && !adapt) return run<64, 64, false>(p, st);
   return DCVC_HIP_EUNSUPPORTED;
 }
-
-// dcvc_set_option("dcb_persistent", 0/1) (A/B switch, via conv.hip)
-extern "C" void dcvc_internal_dcbp_enable(int v) { g_enabled = v; }

@@ -29,6 +29,8 @@
 //     channels, so every t1 value is converted from bf16 once per column,
 //     not once per tap.
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 
 namespace {
 
@@ -518,8 +520,7 @@ __global__ void __launch_bounds__(NTHR) dcbs_kernel(DcbP p) {
   }
 }
 
-int g_cus = 0;
-int g_enabled = 1;
+DCVC_OPTION("dcb_stream", g_enabled, 1);   // 0: no streamed-weight fused DepthConvBlock
 
 template <int CIN, int COUT, bool ADAPT>
 int run(DcbP p, hipStream_t st) {
@@ -528,14 +529,9 @@ int run(DcbP p, hipStream_t st) {
   p.tiles_x = (p.W + TW - 1) / TW;
   p.tiles_y = (p.H + TH - 1) / TH;
   const int64_t ntiles = (int64_t)p.tiles_x * p.tiles_y;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-      return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
-  const int G = ntiles < g_cus ? (int)ntiles : g_cus;
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
+  const int G = ntiles < cus ? (int)ntiles : cus;
   auto kern = dcbs_kernel<CIN, COUT, ADAPT>;
   dcvc_note_kernel("dcbs_kernel<%d, %d, %s>@%lld", CIN, COUT, bname(ADAPT), (long long)G * NTHR);
   dcvc_ensure_lds(reinterpret_cast<const void *>(kern), (int)G_::LDS);
@@ -583,6 +579,3 @@ extern "C" int dcvc_internal_dcbs(const dcvc_dcb_args *a, void *stream) {
   if (a->cin == 64 && a->cout == 128 && adapt) return run<64, 128, true>(p, st);
   return DCVC_HIP_EUNSUPPORTED;
 }
-
-// dcvc_set_option("dcb_stream", 0/1) (A/B switch, via conv.hip)
-extern "C" void dcvc_internal_dcbs_enable(int v) { g_enabled = v; }

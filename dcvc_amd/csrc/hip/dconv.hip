@@ -22,6 +22,8 @@
 //     DEPTH K steps ahead of their MFMAs;
 //   * waves never wait for each other: no barrier after the weight load.
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 #include "split.h"
 
 #include <cstring>
@@ -417,13 +419,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   wait_vm_lgkm();
 }
 
-int g_cus = 0;
-int g_enable = 1;   // dcvc_set_option("dconv", 0): route these layers to sconv.hip
-int g_k1 = 1;       // dcvc_set_option("dconv_1x1", 0): stride-1 1x1 layers to sgemm.hip
-int g_bn128 = 1;   // dcvc_set_option("dconv_bn128", 0): 64-channel n-blocks for 1x1 layers (A/B)
-int g_s2blk = 2;   // dcvc_set_option("dconv_s2blocks", n): most n-blocks of a 3x3 layer (A/B)
-int g_gate = 1;     // dcvc_set_option("dconv_gate", 0): ConvFFN2's gated 1x1 to sconv.hip
-int g_xcd = 1;      // dcvc_set_option("dconv_xcd", 0): n-blocks of a tile on different XCDs (A/B)
+DCVC_OPTION("dconv", g_enable, 1);         // 0: route these layers to sconv.hip
+DCVC_OPTION("dconv_1x1", g_k1, 1);         // 0: stride-1 1x1 layers to sgemm.hip
+DCVC_OPTION("dconv_bn128", g_bn128, 1);    // 0: 64-channel n-blocks for 1x1 layers (A/B)
+DCVC_OPTION("dconv_s2blocks", g_s2blk, 2); // n: most n-blocks of a 3x3 layer (A/B)
+DCVC_OPTION("dconv_gate", g_gate, 1);      // 0: ConvFFN2's gated 1x1 to sconv.hip
+DCVC_OPTION("dconv_xcd", g_xcd, 1);        // 0: n-blocks of a tile on any XCD (1: on different ones; A/B)
 
 template <int KS, int BN, int NP, bool GATE = false>
 int launch(DP p, hipStream_t st) {
@@ -435,16 +436,11 @@ int launch(DP p, hipStream_t st) {
   if (nt <= 0) return DCVC_HIP_OK;
   if (nt > 0x7fffffff) return DCVC_HIP_EINVAL;
   p.ntiles = (int)nt;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-      return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
   // one workgroup per CU, a whole number of output-channel blocks; no more
   // workgroups per block than its tiles need (8 waves each)
-  int64_t per = (g_cus + p.nblk - 1) / p.nblk;
+  int64_t per = (cus + p.nblk - 1) / p.nblk;
   const int64_t need = (nt + 7) / 8;
   if (per > need) per = need;
   if (per < 1) per = 1;
@@ -493,13 +489,6 @@ int pick(DP p, hipStream_t st) {
 
 }  // namespace
 
-extern "C" void dcvc_internal_dconv_enable(int v) { g_enable = v; }
-extern "C" void dcvc_internal_dconv_1x1(int v) { g_k1 = v; }
-extern "C" void dcvc_internal_dconv_xcd(int v) { g_xcd = v; }
-extern "C" void dcvc_internal_dconv_gate(int v) { g_gate = v; }
-extern "C" void dcvc_internal_dconv_s2blocks(int v) { g_s2blk = v; }
-extern "C" void dcvc_internal_dconv_bn128(int v) { g_bn128 = v; }
-
 // Stride-2 3x3 / 1x1 and feature-rate 1x1 f16x3 convolutions with fp32
 // views (dcvc_conv2d tries it before sconv.hip).  DCVC_HIP_EUNSUPPORTED:
 // shapes / views / options it does not take.
@@ -522,66 +511,41 @@ extern "C" int dcvc_internal_dconv(const dcvc_conv_args *a, void *stream) {
   if (a->res2.ptr && !a->res.ptr) return DCVC_HIP_EUNSUPPORTED;
   const bool gate = a->in_op == DCVC_IN_GATE;
   if (gate && (!k1 || !g_gate || a->shuffle)) return DCVC_HIP_EUNSUPPORTED;
-  if (a->in_op != DCVC_IN_NONE && !gate && !(a->in_op == DCVC_IN_LRELU && a->in_slope >= 0.f && a->in_slope <= 1.f))
-    return DCVC_HIP_EUNSUPPORTED;
-  if (a->act != DCVC_ACT_NONE && !(a->act == DCVC_ACT_LRELU && a->slope >= 0.f && a->slope <= 1.f))
-    return DCVC_HIP_EUNSUPPORTED;
+  if (a->in_op != DCVC_IN_NONE && !gate && !(a->in_op == DCVC_IN_LRELU && lrelu_exact(a->in_slope))) return DCVC_HIP_EUNSUPPORTED;
+  if (a->act != DCVC_ACT_NONE && !(a->act == DCVC_ACT_LRELU && lrelu_exact(a->slope))) return DCVC_HIP_EUNSUPPORTED;
   if (a->x.dtype != DCVC_F32 || a->y.dtype != DCVC_F32) return DCVC_HIP_EUNSUPPORTED;
-  if (a->cin % 8 || (uintptr_t)a->x.ptr % 16 || a->x.cstride % 4 || a->x.coff % 4) return DCVC_HIP_EUNSUPPORTED;
-  auto vec_ok = [&](const dcvc_tensor &t) {
-    return (uintptr_t)t.ptr % 16 == 0 && t.cstride % 4 == 0 && t.coff % 4 == 0 && t.dtype == DCVC_F32;
-  };
+  if (a->cin % 8 || !f32_pieces_ok(a->x, 4)) return DCVC_HIP_EUNSUPPORTED;
+  auto vec_ok = [&](const dcvc_tensor &t) { return f32_pieces_ok(t, 4) && t.dtype == DCVC_F32; };
   if (a->res.ptr && (!vec_ok(a->res) || a->cout % 4)) return DCVC_HIP_EUNSUPPORTED;
   if (a->res2.ptr && !vec_ok(a->res2)) return DCVC_HIP_EUNSUPPORTED;
   if (a->shuffle && a->cout % 16 == 0 && !vec_ok(a->y)) return DCVC_HIP_EUNSUPPORTED;
   DP p{};
+  fill_conv_views(p, a);
+  fill_res2_view(p, a);
   // outputs: 16-byte pieces of 4 channels where the view allows, else
   // element stores (SpyNet's 2-channel flow)
-  p.vec_out = (uintptr_t)a->y.ptr % 16 == 0 && a->y.cstride % 4 == 0 && a->y.coff % 4 == 0 && a->cout % 4 == 0;
+  p.vec_out = f32_pieces_ok(a->y, 4) && a->cout % 4 == 0;
   p.ovf = dcvc_internal_split_flag();
-  p.x = reinterpret_cast<const float *>(a->x.ptr);
-  p.H = a->x.H;
-  p.W = a->x.W;
-  p.xcs = a->x.cstride;
-  p.xco = a->x.coff;
-  p.w = reinterpret_cast<const uint16_t *>(a->w);
-  p.y = reinterpret_cast<float *>(a->y.ptr);
   p.S = a->stride;
   p.pad = a->pad;
+  p.H = a->x.H;
+  p.W = a->x.W;
   p.Ho = (a->x.H + 2 * a->pad - a->kh) / a->stride + 1;
   p.Wo = (a->x.W + 2 * a->pad - a->kw) / a->stride + 1;
   const int f = a->shuffle ? 2 : 1;
   if (a->y.H != p.Ho * f || a->y.W != p.Wo * f) return DCVC_HIP_EUNSUPPORTED;
   p.shuffle = a->shuffle ? 1 : 0;
-  if (a->res.ptr) {
-    p.res = reinterpret_cast<const float *>(a->res.ptr);
-    p.rcs = a->res.cstride;
-    p.rco = a->res.coff;
-  }
-  if (a->res2.ptr) {
-    p.res2 = reinterpret_cast<const float *>(a->res2.ptr);
-    p.r2cs = a->res2.cstride;
-    p.r2co = a->res2.coff;
-  }
-  p.ycs = a->y.cstride;
-  p.yco = a->y.coff;
   p.cin = a->cin;
   p.cout = a->cout;
   p.kt = a->kh * a->kw;
-  p.nch = (a->cin + 31) / 32;
-  const int vcl = a->cin - 32 * (p.nch - 1);
-  p.tpkl = vcl <= 8 ? 4 : vcl <= 16 ? 2 : 1;
-  p.nst = (p.nch - 1) * p.kt + (p.kt + p.tpkl - 1) / p.tpkl;
-  p.wchunk = (int64_t)2 * p.kt * a->cout * 32;
-  const int64_t wb = ((int64_t)(p.nch - 1) * p.wchunk + (int64_t)2 * ((p.kt + p.tpkl - 1) / p.tpkl) * a->cout * 32) * 2;
-  if (wb >= ((int64_t)1 << 31) - 64) return DCVC_HIP_EUNSUPPORTED;
-  p.wbytes = (int)wb;
+  const SplitWLayout wl = split_wlayout(a->cin, a->cout, a->kh, a->kw);
+  if (!wl.fits_i32) return DCVC_HIP_EUNSUPPORTED;
+  p.nch = wl.nch;
+  p.tpkl = wl.tpk_last;
+  p.nst = wl.nst;
+  p.wchunk = wl.wchunk;
+  p.wbytes = (int)wl.bytes;
   p.in_lrelu = a->in_op == DCVC_IN_LRELU;
-  p.in_slope = a->in_slope;
-  p.act = a->act;
-  p.slope = a->slope;
-  p.bias = a->bias;
-  p.scale = a->scale;
   // 32-bit element offsets of the input and output maps; the input's buffer
   // record is clamped to 0x7fff0000 bytes (kernel), so a larger input map
   // would read zeros in its last 64 KiB: refused here instead

@@ -7,6 +7,7 @@
 // associative and commutative, so any reduction order gives the same words:
 // the kernels are deterministic by construction and use no atomics.
 #include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -141,20 +142,14 @@ __global__ void __launch_bounds__(kBlock) digest_fold_kernel(const uint64_t *ws,
   }
 }
 
-int g_cus = 0;
-
 }  // namespace
 
 extern "C" int64_t dcvc_digest_workspace(void) { return (int64_t)2 * kMaxBlocks * sizeof(uint64_t); }
 
 extern "C" int dcvc_digest_threads(void) {
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
-  int64_t blocks = (int64_t)g_cus * kBlocksPerCu;
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
+  int64_t blocks = (int64_t)cus * kBlocksPerCu;
   if (blocks > kMaxBlocks) blocks = kMaxBlocks;
   if (blocks < 1) blocks = 1;
   return (int)(blocks * kBlock);

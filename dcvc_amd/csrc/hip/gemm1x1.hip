@@ -12,6 +12,7 @@
 // The epilogue is epilogue.h's: bias, act, residual(s), scale, pixel shuffle.
 #include "common.h"
 #include "epilogue.h"
+#include "options.h"
 
 namespace {
 
@@ -233,7 +234,7 @@ int launch(G1 p, hipStream_t st) {
 // one workgroup per CU: below 768 workgroups at BM = 64 they take BM = 32
 // (where a 2x2 wave layout exists), so each CU holds ~3 workgroups' loads in
 // flight.
-int g_big_bm = 0;  // 0: automatic
+DCVC_OPTION("gemm1x1_bm", g_big_bm, 0);  // 64 | 128 | 256: pixel tile of the full-resolution layers (A/B); anything else: automatic
 
 template <typename TIN, typename TOUT>
 int dispatch(const G1 &p, hipStream_t st) {
@@ -255,8 +256,9 @@ int dispatch(const G1 &p, hipStream_t st) {
   // and 64-pixel tiles (BN <= 32) measured 1.1-2.1x faster (64->64 at
   // 1088x1920: 325 -> 153 us).  dcvc_set_option("gemm1x1_bm", 64 | 128 | 256)
   // forces one size (A/B).
-  if (big && bn <= 64 && g_big_bm != 256) {
-    const bool b128 = g_big_bm == 128 || (g_big_bm == 0 && bn >= 48);
+  const int big_bm = (g_big_bm == 64 || g_big_bm == 128 || g_big_bm == 256) ? g_big_bm : 0;
+  if (big && bn <= 64 && big_bm != 256) {
+    const bool b128 = big_bm == 128 || (big_bm == 0 && bn >= 48);
     switch (bn) {
       case 16: return b128 ? launch<TIN, TOUT, 128, 16, 4>(p, st) : launch<TIN, TOUT, 64, 16, 4>(p, st);
       case 32: return b128 ? launch<TIN, TOUT, 128, 32, 4>(p, st) : launch<TIN, TOUT, 64, 32, 4>(p, st);
@@ -339,4 +341,3 @@ extern "C" int dcvc_internal_gemm1x1(const dcvc_conv_args *a, void *stream) {
   return dispatch<uint16_t, uint16_t>(p, st);
 }
 
-extern "C" void dcvc_internal_gemm1x1_bm(int v) { g_big_bm = (v == 64 || v == 128 || v == 256) ? v : 0; }

@@ -14,6 +14,7 @@
 // 68x120).  LDS row stride: ldk() below.  Epilogue: epilogue.h.
 #include "common.h"
 #include "epilogue.h"
+#include "options.h"
 
 namespace {
 
@@ -112,8 +113,8 @@ __device__ __forceinline__ void direct_epilogue(const GF &p, const f32x4 (&acc)[
 // pixel tile: step s = (32-channel chunk s / 9, tap s % 9), the order of
 // conv.hip's f32 path (chunk-major, taps inside), so again bit-identical;
 // the shifted rows of a tap are contiguous in memory (zero outside the map).
-int g_upfront = 1;  // dcvc_set_option("gemm1x1_f32_upfront", 0/1): step operands read up front (A/B)
-int g_direct = 1;   // dcvc_set_option("gemm1x1_f32_direct", 0/1): epilogue straight from the accumulators (A/B)
+DCVC_OPTION("gemm1x1_f32_upfront", g_upfront, 1);  // 0/1: step operands read up front (A/B)
+DCVC_OPTION("gemm1x1_f32_direct", g_direct, 1);   // 0/1: epilogue straight from the accumulators (A/B)
 
 template <int BM, int BN, int WMW, int KK, bool LIN, bool K3 = false, bool kUpfront = true, bool kDirect = false>
 __global__ void __launch_bounds__(256) gemm1x1f_kernel(GF p) {
@@ -522,9 +523,9 @@ int launch(GF p, hipStream_t st) {
   return DCVC_HIP_OK;
 }
 
-int g_use_gemm_f32 = 1;
-int g_use_k3 = 1;   // dcvc_set_option("gemm3x3_f32", 0/1): fp32 3x3 s1 convs as shifted GEMMs (A/B)
-int g_cfg = 0;  // dcvc_set_option("gemm1x1_f32_cfg", i): force tile config i (A/B), 0 = automatic
+DCVC_OPTION("gemm1x1_f32", g_use_gemm_f32, 1);   // 0: fp32 1x1 s1 convs to the generic kernel
+DCVC_OPTION("gemm3x3_f32", g_use_k3, 1);   // 0/1: fp32 3x3 s1 convs as shifted GEMMs (A/B)
+DCVC_OPTION("gemm1x1_f32_cfg", g_cfg, 0);  // i: force tile config i (A/B), 0 = automatic
 
 // Tile choice, from A/B timings of every configuration on the 68x120 latent
 // shapes (scripts/gemm_f32_bench.py, profiles/r02_gemm_f32.jsonl): 128 x 64
@@ -621,8 +622,3 @@ extern "C" int dcvc_internal_gemm1x1_f32(const dcvc_conv_args *a, void *stream) 
   return dispatch(p, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" void dcvc_internal_gemm1x1_f32_enable(int v) { g_use_gemm_f32 = v; }
-extern "C" void dcvc_internal_gemm3x3_f32_enable(int v) { g_use_k3 = v; }
-extern "C" void dcvc_internal_gemm1x1_f32_cfg(int v) { g_cfg = v; }
-extern "C" void dcvc_internal_gemm1x1_f32_upfront(int v) { g_upfront = v; }
-extern "C" void dcvc_internal_gemm1x1_f32_direct(int v) { g_direct = v; }

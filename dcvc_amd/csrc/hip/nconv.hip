@@ -20,6 +20,8 @@
 // differ from sconv.hip, so the outputs agree with it to the split bound, not
 // bit for bit (tests/test_gpu_nconv.py).
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 #include "split.h"
 
 #include <cstring>
@@ -174,8 +176,7 @@ __global__ void __launch_bounds__(256) nconv_kernel(NP p) {
   }
 }
 
-int g_enable = 1;   // dcvc_set_option("nconv", 0): these layers to sconv.hip
-int g_cus = 0;
+DCVC_OPTION("nconv", g_enable, 1);   // 0: these layers to sconv.hip
 
 template <int KS, int CIN, int COUT>
 int launch(NP p, int in_lrelu, hipStream_t st) {
@@ -185,15 +186,11 @@ int launch(NP p, int in_lrelu, hipStream_t st) {
   if (tasks <= 0) return DCVC_HIP_OK;
   if (tasks > 0x7fffffff) return DCVC_HIP_EINVAL;
   p.ntasks = (int)tasks;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
   // a few tasks per wave, so each wave gathers its weight fragments once
   int64_t grid = (tasks + 4 * 4 - 1) / (4 * 4);
-  if (grid > (int64_t)g_cus * 8) grid = (int64_t)g_cus * 8;
+  if (grid > (int64_t)cus * 8) grid = (int64_t)cus * 8;
   if (grid < 1) grid = 1;
   auto kern = in_lrelu ? nconv_kernel<KS, CIN, COUT, true> : nconv_kernel<KS, CIN, COUT, false>;
   dcvc_note_kernel("nconv_kernel<%d, %d, %d, %s>", KS, CIN, COUT, in_lrelu ? "true" : "false");
@@ -204,8 +201,6 @@ int launch(NP p, int in_lrelu, hipStream_t st) {
 
 }  // namespace
 
-extern "C" void dcvc_internal_nconv_enable(int v) { g_enable = v; }
-
 // Stride-1 7x7 split convolutions with COUT * KS <= 16 output (channel, tap
 // column) pairs: SpyNet's 16 -> 2 (dcvc_conv2d tries it before the other
 // split kernels).  DCVC_HIP_EUNSUPPORTED otherwise.
@@ -213,43 +208,21 @@ extern "C" int dcvc_internal_nconv(const dcvc_conv_args *a, void *stream) {
   if (!g_enable) return DCVC_HIP_EUNSUPPORTED;
   if (a->stride != 1 || a->kh != a->kw || a->pad != a->kh / 2 || a->shuffle) return DCVC_HIP_EUNSUPPORTED;
   if (a->x.dtype != DCVC_F32 || a->y.dtype != DCVC_F32 || !a->bias) return DCVC_HIP_EUNSUPPORTED;
-  if (a->in_op != DCVC_IN_NONE && !(a->in_op == DCVC_IN_LRELU && a->in_slope >= 0.f && a->in_slope <= 1.f))
-    return DCVC_HIP_EUNSUPPORTED;
+  if (a->in_op != DCVC_IN_NONE && !(a->in_op == DCVC_IN_LRELU && lrelu_exact(a->in_slope))) return DCVC_HIP_EUNSUPPORTED;
   if (a->res2.ptr && !a->res.ptr) return DCVC_HIP_EUNSUPPORTED;
   if ((a->res.ptr && a->res.dtype != DCVC_F32) || (a->res2.ptr && a->res2.dtype != DCVC_F32)) return DCVC_HIP_EUNSUPPORTED;
-  if ((uintptr_t)a->x.ptr % 16 || a->x.cstride % 4 || a->x.coff % 4) return DCVC_HIP_EUNSUPPORTED;
+  if (!f32_pieces_ok(a->x, 4)) return DCVC_HIP_EUNSUPPORTED;   // (output and residuals: element accesses)
   if ((int64_t)a->x.H * a->x.W * a->x.cstride * 4 >= ((int64_t)1 << 31) - 64) return DCVC_HIP_EUNSUPPORTED;
   if (a->y.H != a->x.H || a->y.W != a->x.W) return DCVC_HIP_EUNSUPPORTED;
   NP p{};
-  p.x = reinterpret_cast<const float *>(a->x.ptr);
-  p.H = a->x.H;
-  p.W = a->x.W;
-  p.xcs = a->x.cstride;
-  p.xco = a->x.coff;
+  fill_conv_views(p, a);
+  fill_res2_view(p, a);
   p.xbytes = (int)((int64_t)a->x.H * a->x.W * a->x.cstride * 4);
-  p.w = reinterpret_cast<const uint16_t *>(a->w);
-  p.bias = a->bias;
-  p.scale = a->scale;
-  p.y = reinterpret_cast<float *>(a->y.ptr);
-  p.Wo = a->x.W;
-  p.ycs = a->y.cstride;
-  p.yco = a->y.coff;
-  if (a->res.ptr) {
-    p.res = reinterpret_cast<const float *>(a->res.ptr);
-    p.rcs = a->res.cstride;
-    p.rco = a->res.coff;
-  }
-  if (a->res2.ptr) {
-    p.res2 = reinterpret_cast<const float *>(a->res2.ptr);
-    p.r2cs = a->res2.cstride;
-    p.r2co = a->res2.coff;
-  }
+  p.H = a->x.H;
+  p.W = p.Wo = a->x.W;
   p.cout = a->cout;
   p.pad = a->pad;
   p.in_lrelu = a->in_op == DCVC_IN_LRELU;
-  p.in_slope = a->in_slope;
-  p.act = a->act;
-  p.slope = a->slope;
   p.ovf = dcvc_internal_split_flag();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int il = p.in_lrelu;

@@ -44,6 +44,8 @@
 //     order and stores fp32 whole lines per wave instruction.
 #include "common.h"
 #include "epilogue.h"
+#include "launch.h"
+#include "options.h"
 #include "split.h"
 
 #include <utility>
@@ -537,9 +539,8 @@ __global__ void __launch_bounds__(NW * 64) sconv_kernel(SP p) {
   wait_vm_lgkm();   // no LDS-DMA left in flight when the workgroup exits
 }
 
-int g_cus = 0;
-int g_dbg = 0;
-int g_occ = 0;   // dcvc_set_option("sconv_occupancy", n): workgroups per CU (0 = as many as the LDS holds)
+DCVC_OPTION("sconv_dbg", g_dbg, 0);   // mask of timing ablations, wrong results (SP::dbg); 0 in production
+DCVC_OPTION("sconv_occupancy", g_occ, 0);   // n: workgroups per CU (0 = as many as the LDS holds)
 
 template <int KS, int S, int BN, int RW, int NW, bool GATE, bool RES>
 int launch(SP p, hipStream_t st) {
@@ -555,17 +556,12 @@ int launch(SP p, hipStream_t st) {
   if (nt <= 0) return DCVC_HIP_OK;
   if (nt > 0x7fffffff) return DCVC_HIP_EINVAL;
   p.ntiles = (int)nt;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-      return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
   int per_cu = (int)((160 * 1024) / lds);
   if (per_cu > 8 / NW * 2) per_cu = 8 / NW * 2;
   if (g_occ > 0 && g_occ < per_cu) per_cu = g_occ;
-  int64_t G = (int64_t)g_cus * per_cu;
+  int64_t G = (int64_t)cus * per_cu;
   if (G > nt) G = nt;
   // a workgroup keeps one n-block (resident weights, loaded once): the grid
   // stride must be a multiple of the n-block count.  A grid smaller than the
@@ -588,12 +584,12 @@ int launch(SP p, hipStream_t st) {
   return DCVC_HIP_OK;
 }
 
-int g_waves = 8;   // dcvc_set_option("sconv_waves", 4 | 8): waves per workgroup of the streamed-weight kernels
-int g_resident = 1;   // dcvc_set_option("sconv_resident", 0): streamed weights only (A/B)
+DCVC_OPTION("sconv_waves", g_waves, 8);   // 4 | 8: waves per workgroup of the streamed-weight kernels
+DCVC_OPTION("sconv_resident", g_resident, 1);   // 0: streamed weights only (A/B)
 
 // tile rows per wave: the tallest tile that still gives >= 1.5 tiles per CU
 // and whose image prefetch fits the registers, else the smallest
-int g_rw = 0;   // dcvc_set_option("sconv_rw", 1 | 2 | 4): force the tile rows per wave (A/B; 0 = auto)
+DCVC_OPTION("sconv_rw", g_rw, 0);   // 1 | 2 | 4: force the tile rows per wave (A/B; 0 = auto)
 
 template <int KS, int S, int BN, int NW, bool GATE, bool RES>
 int pick_rw_nw(SP p, hipStream_t st) {
@@ -641,12 +637,12 @@ int try_bn(SP p, int bn, hipStream_t st) {
   }
 }
 
-// dcvc_set_option("sconv_res_waves", 4 | 8 | 0 = auto): waves per workgroup of
+// 4 | 8 | 0 = auto: waves per workgroup of
 // the resident kernels; auto = 8 for 3x3 (two waves per SIMD hide each
 // other's LDS and VALU phases: 48->48 at 1080p 548 -> 465 us), 4 for 1x1
 // (a wave per SIMD with the whole register file: 48->192 at 1080p 2300 ->
 // 1056 us)
-int g_res_waves = 0;
+DCVC_OPTION("sconv_res_waves", g_res_waves, 0);
 
 template <int KS, int S, bool GATE>
 int pick_bn(SP p, hipStream_t st) {
@@ -686,13 +682,7 @@ int pick_bn(SP p, hipStream_t st) {
 
 }  // namespace
 
-extern "C" void dcvc_internal_sconv_occupancy(int v) { g_occ = v; }
-extern "C" void dcvc_internal_sconv_dbg(int v) { g_dbg = v; }
-extern "C" void dcvc_internal_sconv_rw(int v) { g_rw = v; }
 extern "C" int dcvc_internal_sgemm(const dcvc_conv_args *a, void *stream);
-extern "C" void dcvc_internal_sconv_waves(int v) { g_waves = v; }
-extern "C" void dcvc_internal_sconv_resident(int v) { g_resident = v; }
-extern "C" void dcvc_internal_sconv_res_waves(int v) { g_res_waves = v; }
 
 // f16x3 convolutions (a->compute == DCVC_F16X3): fp32 input and output views.
 // Kernel sizes 1, 3 (stride 1 or 2) and 7 (stride 1); the ConvFFN2 gate input
@@ -707,62 +697,36 @@ extern "C" int dcvc_internal_sconv(const dcvc_conv_args *a, void *stream) {
     if (r != DCVC_HIP_EUNSUPPORTED) return r;
   }
   SP p{};
+  fill_conv_views(p, a);
+  fill_res2_view(p, a);
   p.ovf = dcvc_internal_split_flag();
-  p.x = reinterpret_cast<const float *>(a->x.ptr);
   p.H = a->x.H;
   p.W = a->x.W;
-  p.xcs = a->x.cstride;
-  p.xco = a->x.coff;
-  p.w = reinterpret_cast<const uint16_t *>(a->w);
-  p.bias = a->bias;
-  p.y = a->y.ptr;
   p.Ho = (a->x.H + 2 * a->pad - a->kh) / a->stride + 1;
   p.Wo = (a->x.W + 2 * a->pad - a->kw) / a->stride + 1;
-  p.ycs = a->y.cstride;
-  p.yco = a->y.coff;
   p.cin = a->cin;
   p.cout = a->cout;
   p.pad = a->pad;
   p.in_op = a->in_op;
-  p.in_slope = a->in_slope;
-  p.act = a->act;
-  p.slope = a->slope;
   p.shuffle = a->shuffle;
-  p.scale = a->scale;
   p.Wout = a->y.W;
-  if (a->res.ptr) {
-    p.res = a->res.ptr;
-    p.rcs = a->res.cstride;
-    p.rco = a->res.coff;
-  }
-  if (a->res2.ptr) {
-    p.res2 = a->res2.ptr;
-    p.r2cs = a->res2.cstride;
-    p.r2co = a->res2.coff;
-  }
-  p.vec = (a->cin % 8 == 0) && (p.xcs % 4 == 0) && (p.xco % 4 == 0) && ((uintptr_t)p.x % 16 == 0);
-  {
-    bool vo = (p.ycs % 8 == 0) && (p.yco % 8 == 0) && ((uintptr_t)p.y % 16 == 0);
-    if (a->res.ptr) vo = vo && (p.rcs % 8 == 0) && (p.rco % 8 == 0) && ((uintptr_t)p.res % 16 == 0);
-    if (a->res2.ptr) vo = vo && (p.r2cs % 8 == 0) && (p.r2co % 8 == 0) && ((uintptr_t)p.res2 % 16 == 0);
-    p.vec_out = vo ? 1 : 0;
-    // the direct epilogue stores 4 channels per lane: needs cout % 4 == 0 and
-    // 16-byte aligned output / residual pieces
-    p.direct = !a->shuffle && a->cout % 4 == 0 && (p.ycs % 4 == 0) && (p.yco % 4 == 0) && ((uintptr_t)p.y % 16 == 0);
-    if (a->res.ptr) p.direct = p.direct && (p.rcs % 4 == 0) && (p.rco % 4 == 0) && ((uintptr_t)p.res % 16 == 0);
-    if (a->res2.ptr) p.direct = p.direct && (p.r2cs % 4 == 0) && (p.r2co % 4 == 0) && ((uintptr_t)p.res2 % 16 == 0);
-  }
-  p.nchunks = (a->cin + 31) / 32;
-  const int vc = a->cin - 32 * (p.nchunks - 1);
-  p.tpk_last = vc <= 8 ? 4 : vc <= 16 ? 2 : 1;
-  const int kt = a->kh * a->kw;
-  p.wchunk = (int64_t)2 * kt * a->cout * 32;
-  {
-    const int rl = (kt + p.tpk_last - 1) / p.tpk_last;
-    const int64_t wb = ((int64_t)(p.nchunks - 1) * p.wchunk + (int64_t)2 * rl * a->cout * 32) * 2;
-    if (wb >= ((int64_t)1 << 31) - 64) return DCVC_HIP_EUNSUPPORTED;
-    p.wbytes = (int)wb;
-  }
+  // the last in line takes every fp32 view and any slope: alignment only picks
+  // the access width.  Output and residual views, where present, in pieces
+  // `elems` channels apart:
+  auto out_pieces_ok = [&](int elems) {
+    return f32_pieces_ok(a->y, elems) && (!a->res.ptr || f32_pieces_ok(a->res, elems)) &&
+           (!a->res2.ptr || f32_pieces_ok(a->res2, elems));
+  };
+  p.vec = a->cin % 8 == 0 && f32_pieces_ok(a->x, 4);
+  p.vec_out = out_pieces_ok(8) ? 1 : 0;
+  // the direct epilogue stores 4 channels per lane
+  p.direct = !a->shuffle && a->cout % 4 == 0 && out_pieces_ok(4);
+  const SplitWLayout wl = split_wlayout(a->cin, a->cout, a->kh, a->kw);
+  if (!wl.fits_i32) return DCVC_HIP_EUNSUPPORTED;
+  p.nchunks = wl.nch;
+  p.tpk_last = wl.tpk_last;
+  p.wchunk = wl.wchunk;
+  p.wbytes = (int)wl.bytes;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool gate = a->in_op == DCVC_IN_GATE;
   switch (a->kh) {

@@ -18,6 +18,7 @@
 // resident in LDS for the launch (packed LDS images, dcvc_dc_pack_weights);
 // the next tile's halo is loaded into registers while the current one runs.
 #include "common.h"
+#include "launch.h"
 #include "split.h"
 
 namespace {
@@ -361,8 +362,6 @@ __global__ void __launch_bounds__(kNT) sdc_kernel(DP p) {
   wait_vm_lgkm();
 }
 
-int g_cus = 0;
-
 template <int CIN, int COUT, bool ADAPT>
 int run(DP p, hipStream_t st) {
   typedef DG<CIN, COUT, ADAPT> G_;
@@ -372,13 +371,9 @@ int run(DP p, hipStream_t st) {
   const int64_t nt = (int64_t)p.tiles_x * ((p.H + TH - 1) / TH);
   if (nt <= 0) return DCVC_HIP_OK;
   p.ntiles = (int)nt;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
-  int G = g_cus;
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
+  int G = cus;
   if (G > p.ntiles) G = p.ntiles;
   auto kern = sdc_kernel<CIN, COUT, ADAPT>;
   dcvc_note_kernel("sdc_kernel<%d, %d, %s>@%lld", CIN, COUT, bname(ADAPT), (long long)G * kNT);

@@ -28,6 +28,8 @@
 // The epilogue adds b2, the activation, the residual (the fp32 input,
 // re-read from L2) and the scale in the reference's order.
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 #include "split.h"
 
 #include <type_traits>
@@ -333,8 +335,7 @@ sffn_kernel(FP p) {
   wait_vm_lgkm();   // no LDS-DMA in flight at exit
 }
 
-int g_cus = 0;
-int g_c128 = 1;   // dcvc_set_option("sffn128", 0): C = 128 feature maps on 4 waves of two pixel tiles (A/B)
+DCVC_OPTION("sffn128", g_c128, 1);   // 0: C = 128 feature maps on 4 waves of two pixel tiles (A/B)
 
 template <int C, int NW, int NP, int NBUF>
 int run(FP p, hipStream_t st) {
@@ -344,13 +345,9 @@ int run(FP p, hipStream_t st) {
   static_assert(G_::LDS <= 160 * 1024, "LDS");
   p.nslices = G_::NS;
   p.ntiles = (p.npix + G_::TP - 1) / G_::TP;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
-  int G = g_cus;
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
+  int G = cus;
   if (G > p.ntiles) G = p.ntiles;
   auto kern = sffn_kernel<C, NW, NP, NBUF>;
   dcvc_note_kernel("sffn_kernel<%d, %d, %d, %d>@%lld", C, NW, NP, NBUF, (long long)G * NW * 64);
@@ -412,8 +409,6 @@ extern "C" int64_t dcvc_ffn_pack_weights(const float *w1, const float *w2, int c
   }
   return slice * ns;
 }
-
-extern "C" void dcvc_internal_sffn128(int v) { g_c128 = v; }
 
 extern "C" int dcvc_conv_ffn(const dcvc_ffn_args *a, void *stream) {
   if (!a || !a->x.ptr || !a->y.ptr || !a->w || !a->b1 || !a->b2) return DCVC_HIP_EINVAL;

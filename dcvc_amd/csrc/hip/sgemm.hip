@@ -26,6 +26,8 @@
 // stages past the last chunk read zeros through out-of-range buffer offsets,
 // so the per-stage vector-memory count is constant and vmcnt can be counted.
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 #include "split.h"
 
 #include <utility>
@@ -375,14 +377,12 @@ int launch(GP p, hipStream_t st) {
   return DCVC_HIP_OK;
 }
 
-// dcvc_set_option("sgemm", v): 0 = auto, -1 = off (sconv.hip's 1x1 path),
+// 0 = auto, -1 = off (sconv.hip's 1x1 path),
 // 1..6 = force (BN, PXW) = (128, 2), (64, 2), (32, 2), (128, 1), (64, 1), (32, 1)
-int g_cfg = 0;
-int g_cus = 0;
-int g_pd = 0;   // dcvc_set_option("sgemm_pd", 1 | 2 | 3 | 5): stages in flight (A/B); 0 = auto
-// dcvc_set_option("sgemm_gate", 0): ConvFFN2's gated 1x1 below dconv.hip's
-// pixel count back to sconv.hip (A/B)
-int g_gate = 1;
+DCVC_OPTION("sgemm", g_cfg, 0);
+DCVC_OPTION("sgemm_pd", g_pd, 0);   // 1 | 2 | 3 | 5: stages in flight (A/B); 0 = auto
+// 0: ConvFFN2's gated 1x1 below dconv.hip's pixel count back to sconv.hip (A/B)
+DCVC_OPTION("sgemm_gate", g_gate, 1);
 
 template <int PD>
 int run_pd(int cfg, const GP &p, hipStream_t st) {
@@ -424,10 +424,6 @@ int run_cfg(int cfg, const GP &p, hipStream_t st) {
 
 }  // namespace
 
-extern "C" void dcvc_internal_sgemm_cfg(int v) { g_cfg = v; }
-extern "C" void dcvc_internal_sgemm_pd(int v) { g_pd = v; }
-extern "C" void dcvc_internal_sgemm_gate(int v) { g_gate = v; }
-
 // The f16x3 1x1 stride-1 convolutions sconv.hip hands over (no pad, no pixel
 // shuffle with a gate, 8-channel aligned input, 4-channel aligned output pieces);
 // DCVC_HIP_EUNSUPPORTED sends the call back to sconv.hip.
@@ -436,61 +432,35 @@ extern "C" int dcvc_internal_sgemm(const dcvc_conv_args *a, void *stream) {
   if (a->kh != 1 || a->kw != 1 || a->stride != 1 || a->pad != 0) return DCVC_HIP_EUNSUPPORTED;
   const bool gate = a->in_op == DCVC_IN_GATE;
   if (a->in_op != DCVC_IN_NONE && a->in_op != DCVC_IN_LRELU && !(gate && g_gate)) return DCVC_HIP_EUNSUPPORTED;
-  // (the kernel's input leaky ReLU is max(v, s v): 0 <= s <= 1)
-  if (a->in_op == DCVC_IN_LRELU && !(a->in_slope >= 0.f && a->in_slope <= 1.f)) return DCVC_HIP_EUNSUPPORTED;
+  if (a->in_op == DCVC_IN_LRELU && !lrelu_exact(a->in_slope)) return DCVC_HIP_EUNSUPPORTED;   // (no rule for the output slope)
   if (gate && a->shuffle) return DCVC_HIP_EUNSUPPORTED;
   if (a->x.dtype != DCVC_F32 || a->y.dtype != DCVC_F32) return DCVC_HIP_EUNSUPPORTED;
   const int f = a->shuffle ? 2 : 1;
   if (a->x.H * f != a->y.H || a->x.W * f != a->y.W) return DCVC_HIP_EUNSUPPORTED;
   if (a->shuffle && (a->cout % 4 || a->y.C * 4 != a->cout)) return DCVC_HIP_EUNSUPPORTED;
-  auto al = [](const void *ptr, int cs, int co) {
-    return ptr == nullptr || ((uintptr_t)ptr % 16 == 0 && cs % 4 == 0 && co % 4 == 0);
-  };
-  if (a->cin % 8 || a->cout % 4 || !al(a->x.ptr, a->x.cstride, a->x.coff) || !al(a->y.ptr, a->y.cstride, a->y.coff) ||
-      !al(a->res.ptr, a->res.cstride, a->res.coff) || !al(a->res2.ptr, a->res2.cstride, a->res2.coff))
-    return DCVC_HIP_EUNSUPPORTED;
-  if ((a->res.ptr && a->res.dtype != DCVC_F32) || (a->res2.ptr && a->res2.dtype != DCVC_F32))
-    return DCVC_HIP_EUNSUPPORTED;
+  // 16-byte pieces everywhere; res2 without res is taken
+  if (a->cin % 8 || a->cout % 4 || !f32_pieces_ok(a->x, 4) || !f32_pieces_ok(a->y, 4)) return DCVC_HIP_EUNSUPPORTED;
+  if (a->res.ptr && !(a->res.dtype == DCVC_F32 && f32_pieces_ok(a->res, 4))) return DCVC_HIP_EUNSUPPORTED;
+  if (a->res2.ptr && !(a->res2.dtype == DCVC_F32 && f32_pieces_ok(a->res2, 4))) return DCVC_HIP_EUNSUPPORTED;
   GP p{};
+  fill_conv_views(p, a);
+  fill_res2_view(p, a);
   p.ovf = dcvc_internal_split_flag();
-  p.x = reinterpret_cast<const float *>(a->x.ptr);
-  p.xcs = a->x.cstride;
-  p.xco = a->x.coff;
   const int64_t np = (int64_t)a->x.H * a->x.W;
   if (np <= 0) return DCVC_HIP_OK;
   if (np > 0x7fffffff - 256) return DCVC_HIP_EUNSUPPORTED;
   p.npix = (int)np;
-  p.w = reinterpret_cast<const uint16_t *>(a->w);
   p.cin = a->cin;
   p.cout = a->cout;
-  p.nchunks = (a->cin + 31) / 32;
-  p.wchunk = (int64_t)2 * a->cout * 32;
-  {
-    const int64_t wb = (int64_t)p.nchunks * p.wchunk * 2;
-    if (wb >= ((int64_t)1 << 31) - 64) return DCVC_HIP_EUNSUPPORTED;
-    p.wbytes = (int)wb;
-  }
+  // (one tap: a narrow last chunk has the one row of a full chunk)
+  const SplitWLayout wl = split_wlayout(a->cin, a->cout, 1, 1);
+  if (!wl.fits_i32) return DCVC_HIP_EUNSUPPORTED;
+  p.nchunks = wl.nch;
+  p.wchunk = wl.wchunk;
+  p.wbytes = (int)wl.bytes;
   p.shuffle = a->shuffle ? 1 : 0;
   p.W = a->x.W;
-  p.bias = a->bias;
-  p.y = reinterpret_cast<float *>(a->y.ptr);
-  p.ycs = a->y.cstride;
-  p.yco = a->y.coff;
   p.in_op = a->in_op;
-  p.in_slope = a->in_slope;
-  p.act = a->act;
-  p.slope = a->slope;
-  p.scale = a->scale;
-  if (a->res.ptr) {
-    p.res = reinterpret_cast<const float *>(a->res.ptr);
-    p.rcs = a->res.cstride;
-    p.rco = a->res.coff;
-  }
-  if (a->res2.ptr) {
-    p.res2 = reinterpret_cast<const float *>(a->res2.ptr);
-    p.r2cs = a->res2.cstride;
-    p.r2co = a->res2.coff;
-  }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (g_cfg > 0) return run_cfg(g_cfg, p, st);
   // auto: n-blocks by padded output channels (fewest first; 64 before 128 on
@@ -498,12 +468,8 @@ extern "C" int dcvc_internal_sgemm(const dcvc_conv_args *a, void *stream) {
   // CU, else 1.  scripts/gpu_r04q.sh (profiles/r04q_sgemm_ab.jsonl): 128 ->
   // 128 at 272x480 49.1 -> 37.0 us, 384 -> 384 at 68x120 18.4 -> 16.3 us, the
   // 1080p 1x1 layers unchanged (BN 128 never ahead)
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
   int order[3] = {64, 128, 32};
   auto padded = [&](int bn) { return (p.cout + bn - 1) / bn * bn - p.cout; };
   for (int i = 0; i < 3; ++i)
@@ -515,7 +481,7 @@ extern "C" int dcvc_internal_sgemm(const dcvc_conv_args *a, void *stream) {
       const int bn = order[i];
       if (padded(bn) > padded(order[0])) break;
       const int64_t nt = (np + 64 * pxw - 1) / (64 * pxw) * ((p.cout + bn - 1) / bn);
-      if (nt >= (pxw == 2 ? 8 : 1) * g_cus) return run_cfg(cfg_of(bn, pxw), p, st);
+      if (nt >= (pxw == 2 ? 8 : 1) * cus) return run_cfg(cfg_of(bn, pxw), p, st);
     }
   return run_cfg(cfg_of(order[0], 1), p, st);
 }

@@ -13,6 +13,8 @@
 // sconv.hip's bit for bit: tests/test_gpu_tconv.py holds it to fp64 and to
 // sconv within the split precision's bound.
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 
 #include <cstring>
 
@@ -164,7 +166,7 @@ __global__ void __launch_bounds__(256) tconv_ci_kernel(TP p) {
   }
 }
 
-int g_enable = 1;   // dcvc_set_option("tconv", 0): these layers to the split kernels
+DCVC_OPTION("tconv", g_enable, 1);   // 0: these layers to the split kernels
 
 template <typename K>
 int launch(K kern, const char *name, int64_t threads, size_t lds, const TP &p, hipStream_t st) {
@@ -180,8 +182,6 @@ int launch(K kern, const char *name, int64_t threads, size_t lds, const TP &p, h
 
 }  // namespace
 
-extern "C" void dcvc_internal_tconv_enable(int v) { g_enable = v; }
-
 // Thin split-precision convolutions (dcvc_conv2d tries it first for
 // DCVC_F16X3 weights): 2-channel-input 3x3 / 1x1 layers of a multiple of 64
 // output channels.  DCVC_HIP_EUNSUPPORTED otherwise.
@@ -196,40 +196,20 @@ extern "C" int dcvc_internal_tconv(const dcvc_conv_args *a, void *stream) {
                   (a->stride == 1 || a->stride == 2);
   if (!ci) return DCVC_HIP_EUNSUPPORTED;
   TP p{};
-  p.x = reinterpret_cast<const float *>(a->x.ptr);
-  p.H = a->x.H;
-  p.W = a->x.W;
-  p.xcs = a->x.cstride;
-  p.xco = a->x.coff;
-  p.w = reinterpret_cast<const uint16_t *>(a->w);
-  p.bias = a->bias;
-  p.scale = a->scale;
-  p.y = reinterpret_cast<float *>(a->y.ptr);
+  fill_conv_views(p, a);
+  fill_res2_view(p, a);
   p.S = a->stride;
   p.pad = a->pad;
+  p.H = a->x.H;
+  p.W = a->x.W;
   p.Ho = (a->x.H + 2 * a->pad - a->kh) / a->stride + 1;
   p.Wo = (a->x.W + 2 * a->pad - a->kw) / a->stride + 1;
   if (a->y.H != p.Ho || a->y.W != p.Wo) return DCVC_HIP_EUNSUPPORTED;
-  p.ycs = a->y.cstride;
-  p.yco = a->y.coff;
-  if (a->res.ptr) {
-    p.res = reinterpret_cast<const float *>(a->res.ptr);
-    p.rcs = a->res.cstride;
-    p.rco = a->res.coff;
-  }
-  if (a->res2.ptr) {
-    p.res2 = reinterpret_cast<const float *>(a->res2.ptr);
-    p.r2cs = a->res2.cstride;
-    p.r2co = a->res2.coff;
-  }
   p.cin = a->cin;
   p.cout = a->cout;
   p.kt = a->kh * a->kw;
   p.in_lrelu = a->in_op == DCVC_IN_LRELU;
-  p.in_slope = a->in_slope;
-  p.act = a->act;
-  p.slope = a->slope;
-  p.vec_out = (uintptr_t)a->y.ptr % 16 == 0 && a->y.cstride % 4 == 0 && a->y.coff % 4 == 0;
+  p.vec_out = f32_pieces_ok(a->y, 4);   // (no rule for the input and residual views or the slopes)
   p.nq = (p.Wo + 3) / 4;
   if (!p.bias) return DCVC_HIP_EUNSUPPORTED;
   // 32-bit buffer offsets of the input map

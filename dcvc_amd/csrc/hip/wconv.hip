@@ -31,6 +31,8 @@
 // chunk counts (48, 64, 128, 192 input channels), n-blocks of 32 or 48
 // channels and at most one residual; the rest stays on xconv.hip.
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 #include "split.h"
 
 #include <algorithm>
@@ -657,9 +659,8 @@ struct SchedEntry {
 const SchedEntry g_sched[] = {WCONV_SCHED(48), WCONV_SCHED(64), WCONV_SCHED(128), WCONV_SCHED(192)};
 #undef WCONV_SCHED
 
-int g_cus = 0;
-int g_dbg = 0;
-int g_enable = 0;   // dcvc_set_option("wconv", 1) routes these layers here (else xconv.hip)
+DCVC_OPTION("wconv_dbg", g_dbg, 0);    // timing-ablation bits, read by -DWCONV_DBG builds only (wrong results)
+DCVC_OPTION("wconv", g_enable, 0);   // 1 routes these layers here (else xconv.hip)
 
 template <int CIN, int BN, int NRES>
 int launch(WP p, hipStream_t st) {
@@ -673,14 +674,9 @@ int launch(WP p, hipStream_t st) {
   if (nt <= 0) return DCVC_HIP_OK;
   if (nt > 0x7fffffff) return DCVC_HIP_EINVAL;
   p.ntiles = (int)nt;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-      return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
-  int64_t grid = g_cus;
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
+  int64_t grid = cus;
   if (grid > nt) grid = nt;
   auto kern = wconv3_kernel<CIN, BN, NRES>;
   dcvc_note_kernel("wconv3_kernel<%d, %d, %d>@%lld", CIN, BN, NRES, (long long)grid * G::NTH);
@@ -710,55 +706,29 @@ extern "C" int dcvc_internal_wconv(const dcvc_conv_args *a, void *stream) {
   if (a->cin != 48 && a->cin != 64 && a->cin != 128 && a->cin != 192) return DCVC_HIP_EUNSUPPORTED;
   if (a->in_op != DCVC_IN_NONE && a->in_op != DCVC_IN_LRELU) return DCVC_HIP_EUNSUPPORTED;
   if (a->x.dtype != DCVC_F32 || a->y.dtype != DCVC_F32) return DCVC_HIP_EUNSUPPORTED;
-  if (a->act != DCVC_ACT_NONE && !(a->act == DCVC_ACT_LRELU && a->slope >= 0.f && a->slope <= 1.f))
-    return DCVC_HIP_EUNSUPPORTED;
-  if (a->in_op == DCVC_IN_LRELU && !(a->in_slope >= 0.f && a->in_slope <= 1.f)) return DCVC_HIP_EUNSUPPORTED;
+  if (a->act != DCVC_ACT_NONE && !(a->act == DCVC_ACT_LRELU && lrelu_exact(a->slope))) return DCVC_HIP_EUNSUPPORTED;
+  if (a->in_op == DCVC_IN_LRELU && !lrelu_exact(a->in_slope)) return DCVC_HIP_EUNSUPPORTED;
   if (a->cout % 32 && a->cout % 48) return DCVC_HIP_EUNSUPPORTED;
   WP p{};
   p.dbg = g_dbg;
   p.ovf = dcvc_internal_split_flag();
-  p.x = reinterpret_cast<const float *>(a->x.ptr);
-  p.H = a->x.H;
-  p.W = a->x.W;
-  p.xcs = a->x.cstride;
-  p.xco = a->x.coff;
-  p.w = reinterpret_cast<const uint16_t *>(a->w);
-  p.y = reinterpret_cast<float *>(a->y.ptr);
-  p.Ho = a->x.H;
-  p.Wo = a->x.W;
-  p.ycs = a->y.cstride;
-  p.yco = a->y.coff;
+  fill_conv_views(p, a);
+  p.H = p.Ho = a->x.H;
+  p.W = p.Wo = a->x.W;
   p.cout = a->cout;
   p.in_lrelu = a->in_op == DCVC_IN_LRELU;
-  p.in_slope = a->in_slope;
-  p.act = a->act;
-  p.slope = a->slope;
-  p.bias = a->bias;
-  p.scale = a->scale;
+  p.has_res = a->res.ptr != nullptr;
   if (a->y.W != p.Wo || a->y.H != p.Ho) return DCVC_HIP_EUNSUPPORTED;
-  bool ok = p.xcs % 4 == 0 && p.xco % 4 == 0 && (uintptr_t)p.x % 16 == 0;
-  ok = ok && p.ycs % 4 == 0 && p.yco % 4 == 0 && (uintptr_t)p.y % 16 == 0;
-  if (a->res.ptr) {
-    p.res = reinterpret_cast<const float *>(a->res.ptr);
-    p.rcs = a->res.cstride;
-    p.rco = a->res.coff;
-    p.has_res = 1;
-    ok = ok && a->res.dtype == DCVC_F32 && p.rcs % 4 == 0 && p.rco % 4 == 0 && (uintptr_t)p.res % 16 == 0;
-  }
-  if (!ok) return DCVC_HIP_EUNSUPPORTED;
+  // 16-byte pieces everywhere
+  if (!f32_pieces_ok(a->x, 4) || !f32_pieces_ok(a->y, 4)) return DCVC_HIP_EUNSUPPORTED;
+  if (a->res.ptr && !(a->res.dtype == DCVC_F32 && f32_pieces_ok(a->res, 4))) return DCVC_HIP_EUNSUPPORTED;
   // per-tile buffer offsets below 2^31 bytes (xconv.hip's bounds)
   if ((int64_t)16 * p.Wo * std::max(p.ycs, p.rcs) * 4 >= ((int64_t)1 << 30)) return DCVC_HIP_EUNSUPPORTED;
   if ((int64_t)19 * p.W * p.xcs * 4 >= 0x7fff0000) return DCVC_HIP_EUNSUPPORTED;
-  const int nch = (a->cin + 31) / 32;
-  const int vc = a->cin - 32 * (nch - 1);
-  const int tpkl = vc <= 8 ? 4 : vc <= 16 ? 2 : 1;
-  p.wchunk = (int64_t)2 * 9 * a->cout * 32;
-  {
-    const int rl = (9 + tpkl - 1) / tpkl;
-    const int64_t wb = ((int64_t)(nch - 1) * p.wchunk + (int64_t)2 * rl * a->cout * 32) * 2;
-    if (wb >= ((int64_t)1 << 31) - 64) return DCVC_HIP_EUNSUPPORTED;
-    p.wbytes = (int)wb;
-  }
+  const SplitWLayout wl = split_wlayout(a->cin, a->cout, 3, 3);
+  if (!wl.fits_i32) return DCVC_HIP_EUNSUPPORTED;
+  p.wchunk = wl.wchunk;
+  p.wbytes = (int)wl.bytes;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   switch (a->cin) {
     case 48: return pick<48>(p, st);
@@ -768,9 +738,6 @@ extern "C" int dcvc_internal_wconv(const dcvc_conv_args *a, void *stream) {
     default: return DCVC_HIP_EUNSUPPORTED;
   }
 }
-
-extern "C" void dcvc_internal_wconv_enable(int v) { g_enable = v; }
-extern "C" void dcvc_internal_wconv_dbg(int v) { g_dbg = v; }
 
 // scripts/check_xconv_vmcnt.py: the producer schedule of instantiation i
 // (cin, bn, nres into prm[3]); DCVC_HIP_EINVAL past the last

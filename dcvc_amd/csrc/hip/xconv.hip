@@ -38,6 +38,8 @@
 // but never read (round 5 loaded a 16-channel chunk's image with the 32-channel
 // chunk's piece count) makes N too large and the wait pass early.
 #include "common.h"
+#include "launch.h"
+#include "options.h"
 #include "split.h"
 
 #include <algorithm>
@@ -1006,15 +1008,13 @@ struct SchedReg {
 template <int CIN, int BN, int RW, int NW, int NRES, int KS>
 SchedReg<CIN, BN, RW, NW, NRES, KS> SchedReg<CIN, BN, RW, NW, NRES, KS>::inst;
 
-int g_cus = 0;
-int g_enable = 1;   // dcvc_set_option("xconv", 0): route every split conv to sconv.hip
-// dcvc_set_option("xconv_dbg", bits) in builds with -DXCONV_DBG (make
-// XCONV_DBG=1): timing ablations, wrong results: 1 no MFMAs,
-// 2 no stage barrier, 4 no weight-DMA wait, 8 no weight DMA, 16 no image
+DCVC_OPTION("xconv", g_enable, 1);   // 0: route every split conv to sconv.hip
+// bits, in builds with -DXCONV_DBG (make XCONV_DBG=1; inert otherwise): timing
+// ablations, wrong results: 1 no MFMAs, 2 no stage barrier, 4 no weight-DMA wait, 8 no weight DMA, 16 no image
 // publish, 32 no image-operand reads, 64 no image loads, 128 no residual loads
 // and output stores
-int g_dbg = 0;
-int g_rw1 = 1;
+DCVC_OPTION("xconv_dbg", g_dbg, 0);
+DCVC_OPTION("xconv_rw1", g_rw1, 1);   // 0: no 8-row tiles of 64-channel blocks for 64-channel residual layers (pick_bn)
 
 template <int CIN, int BN, int RW, int NW, int NRES, bool SHUF = false, int KS = 3>
 int launch(XP p, hipStream_t st) {
@@ -1029,14 +1029,9 @@ int launch(XP p, hipStream_t st) {
   if (nt <= 0) return DCVC_HIP_OK;
   if (nt > 0x7fffffff) return DCVC_HIP_EINVAL;
   p.ntiles = (int)nt;
-  if (g_cus <= 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
-      return DCVC_HIP_ELAUNCH;
-    g_cus = prop.multiProcessorCount;
-  }
-  int64_t grid = (int64_t)g_cus * G::WPC;
+  const int cus = dcvc_cu_count();
+  if (cus <= 0) return DCVC_HIP_ELAUNCH;
+  int64_t grid = (int64_t)cus * G::WPC;
   if (grid > nt) grid = nt;
   auto kern = xconv3_kernel<CIN, BN, RW, NW, NRES, SHUF, KS>;
   // (the name as rocprofv3 prints the instantiation: scripts/pmc_summary.py keys on it)
@@ -1105,8 +1100,6 @@ extern "C" int dcvc_internal_xconv_schedule(int i, int *prm, char *buf, int cap)
   return e.dump(buf, cap);
 }
 
-extern "C" void dcvc_internal_xconv_enable(int v) { g_enable = v; }
-
 // the stamps of the last launch (ablation builds; DCVC_HIP_EUNSUPPORTED otherwise)
 extern "C" int dcvc_internal_xconv_stamps(unsigned *host) {
 #ifdef XCONV_DBG
@@ -1116,20 +1109,6 @@ extern "C" int dcvc_internal_xconv_stamps(unsigned *host) {
   (void)host;
   return DCVC_HIP_EUNSUPPORTED;
 #endif
-}
-extern "C" void dcvc_internal_sconv_dbg(int v);
-extern "C" void dcvc_internal_wconv_dbg(int v);
-extern "C" void dcvc_internal_sconv_rw(int v);
-
-// the split-precision kernels' A/B and timing-ablation options (dcvc_set_option)
-extern "C" int dcvc_internal_set_option_split(const char *name, int value) {
-  if (std::strcmp(name, "sconv_dbg") == 0) dcvc_internal_sconv_dbg(value);
-  else if (std::strcmp(name, "sconv_rw") == 0) dcvc_internal_sconv_rw(value);
-  else if (std::strcmp(name, "xconv_dbg") == 0) g_dbg = value;
-  else if (std::strcmp(name, "xconv_rw1") == 0) g_rw1 = value;
-  else if (std::strcmp(name, "wconv_dbg") == 0) dcvc_internal_wconv_dbg(value);
-  else return DCVC_HIP_EINVAL;
-  return DCVC_HIP_OK;
 }
 
 // 3x3 stride-1 f16x3 convolutions with fp32 views (dcvc_internal_sconv calls
@@ -1146,52 +1125,26 @@ extern "C" int dcvc_internal_xconv(const dcvc_conv_args *a, void *stream) {
   if (a->shuffle && (a->cout % 16 || a->res.ptr || a->res2.ptr)) return DCVC_HIP_EUNSUPPORTED;
   if (a->in_op != DCVC_IN_NONE && a->in_op != DCVC_IN_LRELU) return DCVC_HIP_EUNSUPPORTED;
   if (a->x.dtype != DCVC_F32 || a->y.dtype != DCVC_F32) return DCVC_HIP_EUNSUPPORTED;
-  // leaky ReLUs are computed as max(v, slope v): exact for 0 <= slope <= 1
-  if (a->act != DCVC_ACT_NONE && !(a->act == DCVC_ACT_LRELU && a->slope >= 0.f && a->slope <= 1.f))
-    return DCVC_HIP_EUNSUPPORTED;
-  if (a->in_op == DCVC_IN_LRELU && !(a->in_slope >= 0.f && a->in_slope <= 1.f)) return DCVC_HIP_EUNSUPPORTED;
+  if (a->act != DCVC_ACT_NONE && !(a->act == DCVC_ACT_LRELU && lrelu_exact(a->slope))) return DCVC_HIP_EUNSUPPORTED;
+  if (a->in_op == DCVC_IN_LRELU && !lrelu_exact(a->in_slope)) return DCVC_HIP_EUNSUPPORTED;
   XP p{};
+  fill_conv_views(p, a);
+  fill_res2_view(p, a);
   p.ovf = dcvc_internal_split_flag();
   p.dbg = g_dbg;
-  p.x = reinterpret_cast<const float *>(a->x.ptr);
-  p.H = a->x.H;
-  p.W = a->x.W;
-  p.xcs = a->x.cstride;
-  p.xco = a->x.coff;
-  p.w = reinterpret_cast<const uint16_t *>(a->w);
-  p.y = reinterpret_cast<float *>(a->y.ptr);
-  p.Ho = a->x.H;
-  p.Wo = a->x.W;
-  p.ycs = a->y.cstride;
-  p.yco = a->y.coff;
+  p.H = p.Ho = a->x.H;
+  p.W = p.Wo = a->x.W;
   p.cout = a->cout;
   p.in_lrelu = a->in_op == DCVC_IN_LRELU;
-  p.in_slope = a->in_slope;
-  p.act = a->act;
-  p.slope = a->slope;
-  p.bias = a->bias;
-  p.scale = a->scale;
   p.shuffle = a->shuffle ? 1 : 0;
+  p.has_res = a->res.ptr != nullptr;
+  p.has_res2 = a->res2.ptr != nullptr;
   if (a->y.W != (a->shuffle ? 2 : 1) * p.Wo || a->y.H != (a->shuffle ? 2 : 1) * p.Ho) return DCVC_HIP_EUNSUPPORTED;
   // 16-byte pieces everywhere: input slots of 8 channels, output / residual pieces of 4
-  bool ok = a->cin % 8 == 0 && p.xcs % 4 == 0 && p.xco % 4 == 0 && (uintptr_t)p.x % 16 == 0;
-  ok = ok && a->cout % 4 == 0 && p.ycs % 4 == 0 && p.yco % 4 == 0 && (uintptr_t)p.y % 16 == 0;
-  if (a->res.ptr) {
-    p.res = reinterpret_cast<const float *>(a->res.ptr);
-    p.rcs = a->res.cstride;
-    p.rco = a->res.coff;
-    p.has_res = 1;
-    ok = ok && a->res.dtype == DCVC_F32 && p.rcs % 4 == 0 && p.rco % 4 == 0 && (uintptr_t)p.res % 16 == 0;
-  }
-  if (a->res2.ptr) {
-    p.res2 = reinterpret_cast<const float *>(a->res2.ptr);
-    p.r2cs = a->res2.cstride;
-    p.r2co = a->res2.coff;
-    p.has_res2 = 1;
-    ok = ok && a->res2.dtype == DCVC_F32 && p.r2cs % 4 == 0 && p.r2co % 4 == 0 && (uintptr_t)p.res2 % 16 == 0;
-  }
+  if (a->cin % 8 || !f32_pieces_ok(a->x, 4) || a->cout % 4 || !f32_pieces_ok(a->y, 4)) return DCVC_HIP_EUNSUPPORTED;
+  if (a->res.ptr && !(a->res.dtype == DCVC_F32 && f32_pieces_ok(a->res, 4))) return DCVC_HIP_EUNSUPPORTED;
+  if (a->res2.ptr && !(a->res2.dtype == DCVC_F32 && f32_pieces_ok(a->res2, 4))) return DCVC_HIP_EUNSUPPORTED;
   if (p.has_res2 && !p.has_res) return DCVC_HIP_EUNSUPPORTED;
-  if (!ok) return DCVC_HIP_EUNSUPPORTED;
   // per-tile buffer offsets stay below 2^31 bytes: output / residual rows of
   // a tile (16 rows; with the pixel shuffle 32 rows of 2 Wo pixels) and the
   // input halo rows (16 + 6 at most)
@@ -1200,17 +1153,10 @@ extern "C" int dcvc_internal_xconv(const dcvc_conv_args *a, void *stream) {
   if (a->shuffle && (int64_t)32 * 2 * p.Wo * p.ycs * 4 >= ((int64_t)1 << 31) - 64) return DCVC_HIP_EUNSUPPORTED;
   // (the halo rows a tile reads fit the input record, clamped to 0x7fff0000 bytes)
   if ((int64_t)(16 + a->kh) * p.W * p.xcs * 4 >= 0x7fff0000) return DCVC_HIP_EUNSUPPORTED;
-  const int nch = (a->cin + 31) / 32;
-  const int vc = a->cin - 32 * (nch - 1);
-  const int tpkl = vc <= 8 ? 4 : vc <= 16 ? 2 : 1;
-  const int kt = a->kh * a->kw;
-  p.wchunk = (int64_t)2 * kt * a->cout * 32;
-  {
-    const int rl = (kt + tpkl - 1) / tpkl;
-    const int64_t wb = ((int64_t)(nch - 1) * p.wchunk + (int64_t)2 * rl * a->cout * 32) * 2;
-    if (wb >= ((int64_t)1 << 31) - 64) return DCVC_HIP_EUNSUPPORTED;
-    p.wbytes = (int)wb;
-  }
+  const SplitWLayout wl = split_wlayout(a->cin, a->cout, a->kh, a->kw);
+  if (!wl.fits_i32) return DCVC_HIP_EUNSUPPORTED;
+  p.wchunk = wl.wchunk;
+  p.wbytes = (int)wl.bytes;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #ifdef XCONV_ISA_PROBE
   // (ISA inspection builds, scripts/isa_probe.sh: one channel count, n-block and residual count)

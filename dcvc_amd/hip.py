@@ -74,6 +74,7 @@ HIP_SYMBOLS = [
     ("dcvc_conv_pack_weights", ctypes.c_int64, [_vp, _i, _i, _i, _i, _i, _vp]),
     ("dcvc_conv2d", _i, [ctypes.POINTER(CConvArgs), _vp]),
     ("dcvc_set_option", _i, [ctypes.c_char_p, _i]),
+    ("dcvc_get_option", _i, [ctypes.c_char_p, ctypes.POINTER(_i)]),
     ("dcvc_split_range_flag", _i, [_vp]),
     ("dcvc_last_kernel", ctypes.c_char_p, []),
     ("dcvc_depthconv_block", _i, [ctypes.POINTER(CDcbArgs), _vp]),
@@ -178,6 +179,12 @@ def lib():
 
 def set_option(name, value):
     check(lib().dcvc_set_option(name.encode(), int(value)), "set_option")
+
+
+def get_option(name):
+    v = ctypes.c_int()
+    check(lib().dcvc_get_option(name.encode(), ctypes.byref(v)), "get_option")
+    return v.value
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -386,14 +393,30 @@ def check_canaries():
     return bad
 
 
+def _device(device):
+    return device if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
 def empty(H, W, C, dtype, device=None):
-    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-    return _alloc(H, W, C, dtype, dev, False)
+    return _alloc(H, W, C, dtype, _device(device), False)
 
 
 def zeros(H, W, C, dtype, device=None):
-    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-    return _alloc(H, W, C, dtype, dev, True)
+    return _alloc(H, W, C, dtype, _device(device), True)
+
+
+def _pack(fn, *args, device=None, n=None, dtype=np.uint16):
+    """A dcvc_*_pack_weights call into a new device tensor: fn(*args, NULL)
+    returns the element count (n: the count, for a layout without that
+    query), fn(*args, out) fills the host array.  numpy arguments go by
+    pointer; 16-bit halves travel as int16."""
+    what = fn.__name__[len("dcvc_"):]
+    args = [a.ctypes.data_as(ctypes.c_void_p) if isinstance(a, np.ndarray) else a for a in args]
+    if n is None:
+        n = check(int(fn(*args, None)), what)
+    host = np.zeros(n, dtype=dtype)
+    check(int(fn(*args, host.ctypes.data_as(ctypes.c_void_p))), what)
+    return torch.from_numpy(host.view(np.int16) if dtype == np.uint16 else host).to(_device(device))
 
 
 def from_nchw(x, dtype=F32):
@@ -414,22 +437,11 @@ class ConvW:
         self.stride = stride
         self.pad = (self.kh - 1) // 2
         self.compute = compute
-        cinp = (self.cin + 31) // 32 * 32
-        wn = w.numpy()
-        if compute == F16X3:
-            n = int(check(int(lib().dcvc_conv_pack_weights(wn.ctypes.data_as(ctypes.c_void_p), self.cout, self.cin,
-                                                           self.kh, self.kw, compute, None)), "conv_pack_weights"))
-        else:
-            n = self.cout * self.kh * self.kw * cinp
-        host = np.zeros(n, dtype=np.float32 if compute == F32 else np.uint16)
-        got = lib().dcvc_conv_pack_weights(wn.ctypes.data_as(ctypes.c_void_p), self.cout, self.cin,
-                                           self.kh, self.kw, compute, host.ctypes.data_as(ctypes.c_void_p))
-        check(int(got), "conv_pack_weights")
-        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if compute == F32:
-            self.w = torch.from_numpy(host).to(dev)
-        else:
-            self.w = torch.from_numpy(host.view(np.int16)).to(dev)
+        dev = _device(device)
+        # (the split layout's size comes from the library, the padded ones' from here)
+        n = None if compute == F16X3 else self.cout * self.kh * self.kw * ((self.cin + 31) // 32 * 32)
+        self.w = _pack(lib().dcvc_conv_pack_weights, w.numpy(), self.cout, self.cin, self.kh, self.kw, compute,
+                       device=dev, n=n, dtype=np.float32 if compute == F32 else np.uint16)
         b = bias.detach().float().cpu() if bias is not None else torch.zeros(self.cout)
         self.b = b.contiguous().to(dev)
 
@@ -480,14 +492,8 @@ class FfnW:
         w1 = w1.detach().float().cpu().reshape(w1.shape[0], -1).contiguous().numpy()
         w2 = w2.detach().float().cpu().reshape(w2.shape[0], -1).contiguous().numpy()
         self.hidden, self.c = w1.shape
-        vp = ctypes.c_void_p
-        n = int(lib().dcvc_ffn_pack_weights(w1.ctypes.data_as(vp), w2.ctypes.data_as(vp), self.c, self.hidden, None))
-        check(n, "ffn_pack_weights")
-        host = np.zeros(n, dtype=np.uint16)
-        check(int(lib().dcvc_ffn_pack_weights(w1.ctypes.data_as(vp), w2.ctypes.data_as(vp), self.c, self.hidden,
-                                               host.ctypes.data_as(vp))), "ffn_pack_weights")
-        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.w = torch.from_numpy(host.view(np.int16)).to(dev)
+        dev = _device(device)
+        self.w = _pack(lib().dcvc_ffn_pack_weights, w1, w2, self.c, self.hidden, device=dev)
         self.b1 = b1.detach().float().contiguous().to(dev)
         self.b2 = b2.detach().float().contiguous().to(dev)
 
@@ -502,16 +508,8 @@ class DcW:
         w1n, w2n = f(w1), f(w2)
         wan = f(wa) if wa is not None else None
         self.cin, self.cout = w1n.shape[0], w2n.shape[0]
-        vp = ctypes.c_void_p
-        pa = wan.ctypes.data_as(vp) if wan is not None else None
-        n = int(lib().dcvc_dc_pack_weights(w1n.ctypes.data_as(vp), w2n.ctypes.data_as(vp), pa, self.cin, self.cout,
-                                           None))
-        check(n, "dc_pack_weights")
-        host = np.zeros(n, dtype=np.uint16)
-        check(int(lib().dcvc_dc_pack_weights(w1n.ctypes.data_as(vp), w2n.ctypes.data_as(vp), pa, self.cin,
-                                             self.cout, host.ctypes.data_as(vp))), "dc_pack_weights")
-        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.w = torch.from_numpy(host.view(np.int16)).to(dev)
+        dev = _device(device)
+        self.w = _pack(lib().dcvc_dc_pack_weights, w1n, w2n, wan, self.cin, self.cout, device=dev)
         g = lambda t: t.detach().float().contiguous().to(dev)  # noqa: E731
         self.b1, self.w9c, self.bdw, self.b2 = g(b1), g(w9c), g(bdw), g(b2)
         self.ba = g(ba) if wa is not None else None
@@ -525,13 +523,8 @@ class DwcW:
     def __init__(self, w9c, bdw, w2, b2, device=None):
         w = w2.detach().float().cpu().reshape(w2.shape[0], -1).contiguous().numpy()
         self.c = int(w.shape[0])
-        vp = ctypes.c_void_p
-        n = int(check(int(lib().dcvc_frag_pack_weights(w.ctypes.data_as(vp), self.c, self.c, None)), "frag_pack"))
-        host = np.zeros(n, dtype=np.uint16)
-        check(int(lib().dcvc_frag_pack_weights(w.ctypes.data_as(vp), self.c, self.c, host.ctypes.data_as(vp))),
-              "frag_pack")
-        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.w2 = torch.from_numpy(host.view(np.int16)).to(dev)
+        dev = _device(device)
+        self.w2 = _pack(lib().dcvc_frag_pack_weights, w, self.c, self.c, device=dev)
         g = lambda t: t.detach().float().contiguous().to(dev)  # noqa: E731
         self.w9c, self.bdw, self.b2 = g(w9c), g(bdw), g(b2)
 

@@ -99,12 +99,15 @@ typedef struct dcvc_conv_args {
 int64_t dcvc_conv_pack_weights(const float *w, int cout, int cin, int kh,
                                int kw, int compute, void *out);
 int dcvc_conv2d(const dcvc_conv_args *a, void *stream);
-/* Runtime switches (testing / A-B): "gemm1x1" = 1 (default) routes 1x1
- * stride-1 bf16 convs to the double-buffered GEMM kernel; "conv3x3" = 1
- * (default) routes 3x3 stride-1 bf16 convs to the fixed-geometry kernels;
- * "conv3x3_resident" = 1 (default) prefers its persistent resident-weight
- * variant where the weights fit in LDS. */
+/* Runtime switches (testing / A-B), one int each.  The table is built from
+ * the DCVC_OPTION("name", variable, default) declarations in
+ * dcvc_amd/csrc/hip/ (options.h); each sits beside the code that reads it,
+ * and the comment beside it is the option's documentation.
+ * dcvc_get_option reads the current value back.  Both return
+ * DCVC_HIP_EINVAL for a name that is not in the table.  Setting an option
+ * is not synchronised with launches on other host threads. */
 int dcvc_set_option(const char *name, int value);
+int dcvc_get_option(const char *name, int *value);
 /* fp16 range guard of the split-fp16 kernels (compute DCVC_F16X3 and the fused
  * split blocks): a split operand carries an fp32 value v as hi + 2^-11 lo of two
  * fp16 numbers, to ~2^-21 of v while |v| < 2^15, and saturates silently above.

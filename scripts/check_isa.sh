@@ -17,6 +17,8 @@ trap 'rm -rf "$T"' EXIT
 bad=0
 for o in "$@"; do
   n=$(basename "$o" .o)
+  # a host-only object (options.hip: no kernel, no device variable) carries no code object
+  "$B/llvm-objdump" -h "$o" | grep -q '\.hip_fatbin' || continue
   "$B/llvm-objcopy" --dump-section .hip_fatbin="$T/$n.fat" "$o"
   "$B/clang-offload-bundler" --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 \
     --input="$T/$n.fat" --output="$T/$n.co"
