@@ -40,7 +40,20 @@ relative in the scales pass as ties, one index in a thousand flipped; the
 count does not: IDX_RATE caps the differing indexes of a frame (before its
 first flipped symbol, or in the replay) at 1e-4 of the indexes compared (the
 codec's frames show 1-25 per million).
+
+The decoded picture buffer.  The symbols and pixels above do not see an error
+of 1e-4 relative in ref_feature (tests/test_freerun_bar.py shows it on the
+CPU), so the tensors a P-frame hands to the next one are compared directly
+(compare_dpb / check_dpb): max |product - oracle| over max |oracle| per tensor,
+against the oracle's own reordering noise.  That noise is measured, not chosen:
+tests/golden/make_golden_freerun.py runs the oracle with 16 threads and again
+with 1, each on its own DPB, and records per tensor the largest relative
+difference of a whole GOP in tests/golden/freerun_selfnoise.json.  The bar is
+DPB_FACTOR[precision] times that figure.
 """
+import json
+import os
+
 import numpy as np
 
 SYM_TIE_EPS = 1e-5    # symbol: distance of y - means to the half-integer (largest first flip seen: 4.2e-7)
@@ -51,6 +64,100 @@ TIE_EPS = SYM_TIE_EPS  # the symbols the replay forces (oracle.*.Forcer)
 PSNR_DB = 1e-4        # BASELINE.json: PSNR delta < 1e-4 dB
 REC_MAXABS = 1e-5     # decoded pixel values (0..1), product vs oracle / replay (DC: largest seen <= 1e-5)
 REC_MAXABS_HEM = 1e-4  # ... DCVC-HEM (largest seen 4.4e-5, C2 1080p split; 1/39 of an 8-bit level)
+# DPB tensors: allowed rel = factor x the oracle's recorded self-noise (freerun_selfnoise.json).
+#   parity: the same fp32 products as the oracle in another summation order; 4 covers an MFMA
+#           K-blocking that differs more from either CPU order than the two CPU orders from each other.
+#   split:  each product carries 2^-21 instead of 2^-24 (8x), times 2 for the spread of a maximum
+#           taken over one seed.
+DPB_FACTOR = {"parity": 4, "split": 16}
+GROWTH = 2.0          # last quarter of a free run vs the first quarter of its P-frames (oracle vs itself: ~1)
+DPB_KEYS = ("ref_frame", "ref_feature", "ref_mv_feature", "ref_y", "ref_mv_y")
+SELFNOISE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "freerun_selfnoise.json")
+
+
+def selfnoise(case, unmeasured=None):
+    """{key: rel} of a case of the committed fixture.  ``unmeasured``: the case whose figure stands
+    in for a tensor on which this case's two runs agreed to the bit (rel 0: at 256x256 the motion
+    path is too small for the thread count to reorder its sums), which says nothing about noise."""
+    with open(SELFNOISE) as f:
+        cases = json.load(f)["cases"]
+    out = {k: v["rel"] for k, v in cases[case]["dpb"].items()}
+    if unmeasured is not None:
+        out.update({k: cases[unmeasured]["dpb"][k]["rel"] for k, v in out.items() if v == 0})
+    return out
+
+
+def dpb_view(v):
+    """torch view of a DPB entry (Act, tensor or None)."""
+    return v.t() if hasattr(v, "buf") else v
+
+
+def keep_dpb(dpb):
+    """A copy of a DPB that later frames cannot touch."""
+    return {k: (None if v is None else dpb_view(v).clone()) for k, v in dpb.items()}
+
+
+def _chw(v):
+    """A DPB entry as a float32 (C, H, W) array: an Act is (H, W, C), a tensor (1, C, H, W)."""
+    t = dpb_view(v)
+    t = t.permute(2, 0, 1) if hasattr(v, "buf") else t.reshape(t.shape[-3:])
+    return t.detach().float().cpu().numpy()
+
+
+def compare_dpb(prod_dpb, oracle_dpb, h, w, noise=None, factor=None):
+    """Per DPB key {"maxabs", "rel", "bar", "ratio"}: rel = max |product - oracle| / max |oracle| in float64;
+    ref_frame clamped to [0, 1] and cropped to h x w, the other tensors whole.  bar = factor *
+    noise[key] (None where no noise is given), ratio = rel / bar.  A key that is None on one side
+    must be None on both."""
+    out = {}
+    for k in DPB_KEYS:
+        if k not in oracle_dpb and k not in prod_dpb:
+            continue
+        a, b = prod_dpb.get(k), oracle_dpb.get(k)
+        if a is None or b is None:
+            assert a is None and b is None, f"{k}: None on one side only"
+            continue
+        a, b = _chw(a), _chw(b)
+        if k == "ref_frame":
+            a, b = np.clip(a[:, :h, :w], 0, 1), np.clip(b[:, :h, :w], 0, 1)
+        assert a.shape == b.shape, (k, a.shape, b.shape)
+        # the differences in float64, a channel at a time (a 4K ref_feature is 1.6 GB in fp32)
+        maxabs = max(float(np.abs(a[c].astype(np.float64) - b[c]).max()) for c in range(a.shape[0]))
+        bar = factor * noise[k] if noise is not None else None   # a tensor without a recorded noise is an error
+        rel = maxabs / float(np.abs(b).max())
+        out[k] = {"maxabs": maxabs, "rel": rel, "bar": bar, "ratio": rel / bar if bar else None}
+    return out
+
+
+def dpb_over(d):
+    """The keys of compare_dpb's dict that miss their bar (NaN misses)."""
+    return {k: v for k, v in d.items() if v["bar"] is not None and not v["rel"] <= v["bar"]}
+
+
+def check_dpb(d, name=""):
+    bad = dpb_over(d)
+    assert not bad, f"{name} DPB over the bar: " + ", ".join(
+        f"{k} rel={v['rel']:.3g} > {v['bar']:.3g} ({v['rel'] / v['bar']:.2f}x)" for k, v in bad.items())
+
+
+def growth(rows, gop):
+    """rows[t]: {key: rel} of frame t of a free run.  Per key {"first", "last", "ratio"}: the largest
+    rel over the first quarter of the P-frames and over the last quarter of the frames."""
+    n = len(rows)
+    pf = [t for t in range(n) if t % gop]
+    first, last = pf[:-(-len(pf) // 4)], range(n - max(1, n // 4), n)
+    out = {}
+    for k in DPB_KEYS:
+        a = [rows[t][k] for t in first if k in rows[t]]
+        b = [rows[t][k] for t in last if k in rows[t]]
+        if a and b:
+            out[k] = {"first": max(a), "last": max(b), "ratio": max(b) / max(a) if max(a) > 0 else float(max(b) > 0)}
+    return out
+
+
+def check_growth(g, name=""):
+    bad = {k: v for k, v in g.items() if not v["last"] <= GROWTH * v["first"]}
+    assert not bad, f"{name} DPB difference grows over the run: {bad}"
 
 
 def idx_allowed(n):

@@ -13,6 +13,8 @@ import struct
 import pytest
 import torch
 
+from tests.parity import dpb_view as _t, keep_dpb as keep
+
 pytestmark = pytest.mark.gpu
 
 
@@ -67,11 +69,6 @@ def hem_enc_nets(hem_golden):
     return hem_nets(hem_golden)
 
 
-def _t(v):
-    """torch view of a DPB entry (Act, tensor or None)."""
-    return v.t() if hasattr(v, "buf") else v
-
-
 def assert_dpb_equal(a, b, what):
     assert set(a) == set(b), what
     for k in a:
@@ -82,11 +79,6 @@ def assert_dpb_equal(a, b, what):
         if k == "ref_frame":
             assert ta.dim() == 4 and tb.dim() == 4
         assert ta.shape == tb.shape and torch.equal(ta, tb), (what, k)
-
-
-def keep(dpb):
-    """A copy of a DPB that later frames cannot touch."""
-    return {k: (None if v is None else _t(v).clone()) for k, v in dpb.items()}
 
 
 def reference_loop(kind, inet, pnet, xs, h, w, q, gop, folder):
