@@ -353,7 +353,7 @@ _CANARY_BYTES = 4096
 # Debug aid (DCVC_POISON=nan|rand): every K.empty activation starts as NaN or
 # as random bits (different per allocation) instead of whatever the caching
 # allocator hands back, so a kernel that reads elements nobody wrote shows up
-# as NaN or as an encoder/decoder divergence.
+# as NaN or as an encoder/decoder divergence.  Applies to canary allocations too.
 POISON = os.environ.get("DCVC_POISON", "")
 
 
@@ -379,6 +379,8 @@ def _alloc(H, W, C, dtype, dev, zero):
     flat[n * es:].fill_(0xA5)
     if zero:
         flat[:n * es].zero_()
+    elif POISON:
+        _poison(flat[:n * es].view(_TORCH[dtype]))
     CANARY.append((flat, n * es, (H, W, C, dtype), "".join(traceback.format_stack(limit=6)[:-2])))
     return Act(flat[:n * es].view(_TORCH[dtype]).view(H, W, C))
 

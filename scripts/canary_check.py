@@ -3,6 +3,7 @@ activation allocated with a 4 KiB canary tail (dcvc_amd.hip.CANARY) and
 report allocations whose tail was written.
 
     python scripts/canary_check.py [--model dc|hem] [--frames 3] [--h 1080 --w 1920]
+                                    [--precision split|parity|fast|fast_bf16]
 """
 import argparse
 import os
@@ -19,6 +20,8 @@ def main():
     ap.add_argument("--frames", type=int, default=3)
     ap.add_argument("--h", type=int, default=1080)
     ap.add_argument("--w", type=int, default=1920)
+    ap.add_argument("--precision", default="split", choices=["split", "parity", "fast", "fast_bf16"],
+                    help="split: the shipped path; fast_bf16: bf16 maps and bf16 latent compute")
     args = ap.parse_args()
     import bench
     from dcvc_amd import hip as K
@@ -28,7 +31,8 @@ def main():
     K.CANARY = []
     dev = torch.device("cuda", 0)
     isd, psd = bench.make_weights(None, 0, dev, args.model)
-    prec = Precision.fast(latent_compute=K.BF16)
+    prec = {"split": Precision.split, "parity": Precision.parity, "fast": Precision.fast,
+            "fast_bf16": lambda: Precision.fast(latent_compute=K.BF16)}[args.precision]()
     hem = args.model == "hem"
     if hem:
         from dcvc_amd.hem import DMC, IntraNoAR

@@ -4,7 +4,7 @@ output for NaN.  The first kernel whose NaN-free inputs give a NaN output
 reads LDS it never wrote (its result then depends on whatever a previous or
 concurrent kernel left in LDS).
 
-    python scripts/lds_poison_check.py [--model dc|hem] [--frames 2]
+    python scripts/lds_poison_check.py [--model dc|hem] [--frames 2] [--precision split|parity|fast|fast_bf16]
 """
 import argparse
 import os
@@ -22,6 +22,8 @@ def main():
     ap.add_argument("--h", type=int, default=1080)
     ap.add_argument("--w", type=int, default=1920)
     ap.add_argument("--vgpr", action="store_true", help="also poison VGPRs before every launch")
+    ap.add_argument("--precision", default="split", choices=["split", "parity", "fast", "fast_bf16"],
+                    help="split: the shipped path; fast_bf16: bf16 maps and bf16 latent compute")
     args = ap.parse_args()
     import bench
     from dcvc_amd import hip as K
@@ -36,7 +38,8 @@ def main():
         return bool(torch.isnan(b.float()).any())
 
     for name in ("conv", "flow_warp", "offset_diversity", "resize2x", "depthconv_block", "dwconv3x3",
-                 "pool2x2", "add", "copy", "se_scale", "se_apply", "channel_div"):
+                 "pool2x2", "add", "copy", "se_scale", "se_apply", "channel_div", "conv_ffn", "depth_conv_split",
+                 "dw_conv2_split"):
         if not hasattr(K, name):
             continue
         f = getattr(K, name)
@@ -56,7 +59,8 @@ def main():
         setattr(K, name, wrap)
 
     isd, psd = bench.make_weights(None, 0, dev, args.model)
-    prec = Precision.fast(latent_compute=K.BF16)
+    prec = {"split": Precision.split, "parity": Precision.parity, "fast": Precision.fast,
+            "fast_bf16": lambda: Precision.fast(latent_compute=K.BF16)}[args.precision]()
     hem = args.model == "hem"
     if hem:
         from dcvc_amd.hem import DMC, IntraNoAR
