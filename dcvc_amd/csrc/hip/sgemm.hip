@@ -74,7 +74,7 @@ struct GG {
   static_assert((PD - 1) * L < 64, "vmcnt is 6 bits");
 };
 
-constexpr int kOob = 0x7fffffe0;
+constexpr int kOob = 0x7fffffe0;   // a buffer offset past any num_records: the load returns zeros
 
 // f(integral_constant<int, I>) for I = 0 .. N - 1, in order
 template <typename F, int... I>
@@ -84,7 +84,7 @@ __device__ __forceinline__ void sfor_(F &&f, std::integer_sequence<int, I...>) {
 template <int N, typename F>
 __device__ __forceinline__ void sfor(F &&f) {
   sfor_(f, std::make_integer_sequence<int, N>{});
-}   // a buffer offset past any num_records: the load returns zeros
+}
 
 template <int BN, int PXW, int PD, bool GATE>
 __global__ void __launch_bounds__(256) sgemm_kernel(GP p) {

@@ -531,9 +531,21 @@ extern "C" int64_t dcvc_frag_pack_weights(const float *w, int rows, int k, void 
   return n;
 }
 
+extern "C" int dcvc_internal_dctail(const dcvc_dwc_args *a, void *stream);   // sdct.hip
+
 extern "C" int dcvc_dw_conv2_split(const dcvc_dwc_args *a, void *stream) {
   if (!a || !a->t.ptr || !a->r.ptr || !a->y.ptr || !a->w9 || !a->bdw || !a->w2 || !a->b2) return DCVC_HIP_EINVAL;
   const int c = a->c;
+  if (a->cx || a->cout) {
+    // the feature-rate tail (sdct.hip): its own widths for r and y, an optional adaptor
+    if (a->cx <= 0 || a->cout <= 0 || (a->wa != nullptr) != (a->ba != nullptr)) return DCVC_HIP_EINVAL;
+    if (!a->wa && (a->cx != c || a->cout != c)) return DCVC_HIP_EINVAL;
+    if (a->t.dtype != DCVC_F32 || a->r.dtype != DCVC_F32 || a->y.dtype != DCVC_F32 || a->t.C != c ||
+        a->r.C != a->cx || a->y.C != a->cout || a->t.H != a->y.H || a->t.W != a->y.W || a->r.H != a->y.H ||
+        a->r.W != a->y.W)
+      return DCVC_HIP_EINVAL;
+    return dcvc_internal_dctail(a, stream);
+  }
   if (a->t.dtype != DCVC_F32 || a->r.dtype != DCVC_F32 || a->y.dtype != DCVC_F32 || a->t.C != c || a->r.C != c ||
       a->y.C != c || a->t.H != a->y.H || a->t.W != a->y.W || a->r.H != a->y.H || a->r.W != a->y.W)
     return DCVC_HIP_EINVAL;

@@ -65,7 +65,8 @@ class CDcArgs(ctypes.Structure):
 
 class CDwcArgs(ctypes.Structure):
     _fields_ = [("t", CTensor), ("r", CTensor), ("y", CTensor), ("c", ctypes.c_int), ("w9", ctypes.c_void_p),
-                ("bdw", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p)]
+                ("bdw", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("cx", ctypes.c_int), ("cout", ctypes.c_int), ("wa", ctypes.c_void_p), ("ba", ctypes.c_void_p)]
 
 
 _T = CTensor
@@ -549,6 +550,55 @@ def dw_conv2_split(dwc, t, r, y=None):
         kname = lib().dcvc_last_kernel().decode()
         _t1(e0, kname.split("<")[0], 2 * n * dwc.c * (9 + dwc.c), n * dwc.c * 4 * 3 + dwc.w2.numel() * 2,
             f"{kname} | dw+conv2 {dwc.c} {t.H}x{t.W} f16x3")
+    return y
+
+
+class DcTailW:
+    """The tail of a feature-rate DepthConv packed for the sdct kernel
+    (dcvc_dw_conv2_split with cx / cout set): the depthwise taps w9c [9][c]
+    (device) and bias, conv2 [cout][c] and the adaptor [cout][cx] (or None)
+    as MFMA fragments (dcvc_frag_pack_weights), and their biases."""
+
+    def __init__(self, w9c, bdw, w2, b2, wa=None, ba=None, device=None):
+        f = lambda w: w.detach().float().cpu().reshape(w.shape[0], -1).contiguous().numpy()  # noqa: E731
+        w2n = f(w2)
+        self.cout, self.c = (int(s) for s in w2n.shape)
+        dev = _device(device)
+        self.w2 = _pack(lib().dcvc_frag_pack_weights, w2n, self.cout, self.c, device=dev)
+        g = lambda t: t.detach().float().contiguous().to(dev)  # noqa: E731
+        self.w9c, self.bdw, self.b2 = g(w9c), g(bdw), g(b2)
+        self.cx, self.wa, self.ba = self.c, None, None
+        if wa is not None:
+            wan = f(wa)
+            self.cx = int(wan.shape[1])
+            self.wa = _pack(lib().dcvc_frag_pack_weights, wan, self.cout, self.cx, device=dev)
+            self.ba = g(ba)
+
+
+def dc_tail_split(tw, t, x, y=None):
+    """y = conv2(dw3x3(t) + bdw) + b2 + (adaptor(x) + ba | x) in one kernel
+    (sdct.hip through dcvc_dw_conv2_split); None when no kernel is
+    instantiated for the widths, the views cannot be taken or the "dctail"
+    option is off: the caller runs its earlier route."""
+    if y is None:
+        y = empty(t.H, t.W, tw.cout, F32, t.buf.device)
+    a = CDwcArgs()
+    a.t, a.r, a.y, a.c, a.cx, a.cout = t.c(), x.c(), y.c(), tw.c, tw.cx, tw.cout
+    a.w9, a.bdw, a.w2, a.b2 = tw.w9c.data_ptr(), tw.bdw.data_ptr(), tw.w2.data_ptr(), tw.b2.data_ptr()
+    if tw.wa is not None:
+        a.wa, a.ba = tw.wa.data_ptr(), tw.ba.data_ptr()
+    e0 = _t0()
+    rc = lib().dcvc_dw_conv2_split(ctypes.byref(a), stream())
+    if rc == UNSUPPORTED:
+        return None
+    check(rc, "dc_tail_split")
+    if e0 is not None:
+        n = t.H * t.W
+        kname = lib().dcvc_last_kernel().decode()
+        nw = tw.w2.numel() + (tw.wa.numel() if tw.wa is not None else 0)
+        fl = 2 * n * (9 * tw.c + tw.c * tw.cout + (tw.cx * tw.cout if tw.wa is not None else 0))
+        _t1(e0, kname.split("<")[0], fl, n * (tw.c + tw.cx + tw.cout) * 4 + nw * 2,
+            f"{kname} | dctail {tw.c}+{tw.cx}->{tw.cout} {t.H}x{t.W} f16x3")
     return y
 
 

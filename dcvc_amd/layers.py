@@ -29,6 +29,8 @@ FUSE_DC = True    # split precision: fused DepthConv kernel (sdc.hip) where inst
 DW128 = True      # split precision: the 128-channel feature-rate DepthConv tail (depthwise + conv2 + identity) in one kernel (A/B)
 # (cin, cout, adaptor) of the fused DepthConv instantiations (sdc.hip supported())
 SDC_SHAPES = {(64, 48, True), (48, 32, True), (32, 64, True), (64, 64, False), (48, 48, False), (32, 32, False)}
+# (cin, cout, adaptor) of the feature-rate DepthConv tail instantiations (sdct.hip dcvc_internal_dctail)
+SDCT_SHAPES = {(128, 64, True), (64, 128, True), (128, 128, False)}
 
 
 class Precision:
@@ -319,6 +321,16 @@ class DepthConvBlock:
         if (FUSE_DC and self.conv1.compute == F16X3 and self.adaptor is None and self.conv1.cin == self.conv2.cout
                 and ((latent and self.conv2.cin in (192, 384)) or (DW128 and not latent and self.conv2.cin == 128))):
             self.dwc = K.DwcW(self.dw[0], self.dw[1], sd[d + ".conv2.weight"], sd[d + ".conv2.bias"], ctx.dev)
+        # split precision, the feature-rate blocks sdc.hip does not take (the
+        # reconstruction UNets, the mv branch): depthwise + conv2 + adaptor /
+        # identity in one kernel (sdct.hip; the library's "dctail" option
+        # switches it off, the block then runs its earlier route)
+        self.dct = None
+        if (FUSE_DC and self.conv1.compute == F16X3 and not latent and
+                (self.conv1.cin, self.conv2.cout, self.adaptor is not None) in SDCT_SHAPES):
+            self.dct = K.DcTailW(self.dw[0], self.dw[1], sd[d + ".conv2.weight"], sd[d + ".conv2.bias"],
+                                 sd[d + ".adaptor.weight"] if self.adaptor is not None else None,
+                                 sd[d + ".adaptor.bias"] if self.adaptor is not None else None, ctx.dev)
         self.ffn = None
         # (sffn.hip for the feature-rate widths; slffn.hip for the latent
         # 192 / 384-channel blocks of the entropy model)
@@ -340,14 +352,12 @@ class DepthConvBlock:
         dc = None
         if self.dcw is not None:
             dc = K.depth_conv_split(self.dcw, x, slope=self.slope_dc)
-        if dc is not None:
-            pass
-        elif self.adaptor is not None:
-            idn = K.conv(self.adaptor, x, out_dtype=dt)
-        else:
-            idn = cast(x, dt)
         if dc is None:
             t = K.conv(self.conv1, x, out_dtype=dt, act=ACT_LRELU, slope=self.slope_dc)
+            if self.dct is not None and dt == F32 and x.dtype == F32:
+                dc = K.dc_tail_split(self.dct, t, x)
+        if dc is None:
+            idn = K.conv(self.adaptor, x, out_dtype=dt) if self.adaptor is not None else cast(x, dt)
             if self.dwc is not None:
                 dc = K.dw_conv2_split(self.dwc, t, idn)
             if dc is None:

@@ -184,6 +184,18 @@ int dcvc_conv_ffn(const dcvc_ffn_args *a, void *stream);
  * fragments, hi and lo planes; out NULL returns the element count).
  * Replaces the depthwise launch and the conv2 launch of the unfused block
  * with identical results.  DCVC_HIP_EUNSUPPORTED for other widths.
+ *
+ * With cx and cout set (both 0 above) the call asks for the feature-rate
+ * tail kernel (sdct.hip, option "dctail") of the blocks the fused DepthConv
+ * below does not take:
+ *   y = conv2(dw3x3(t) + bdw) + b2 + idn,  idn = adaptor(r) + ba  or  r
+ * t has c channels, r has cx, y has cout; w2 = conv2 [cout][c] and wa = the
+ * adaptor [cout][cx] (NULL: none, cx = cout = c) packed by
+ * dcvc_frag_pack_weights.  (c, cx, cout) in {(128, 128, 64), (64, 64, 128)}
+ * with an adaptor, (128, 128, 128) without; any H x W.  Identical results
+ * to the depthwise launch and the two 1x1 launches it replaces.
+ * DCVC_HIP_EUNSUPPORTED for other shapes and for views the kernel cannot
+ * take (the caller runs its earlier route).
  */
 typedef struct dcvc_dwc_args {
   dcvc_tensor t, r, y;
@@ -191,6 +203,9 @@ typedef struct dcvc_dwc_args {
   const float *w9, *bdw;
   const void *w2;
   const float *b2;
+  int cx, cout;
+  const void *wa;
+  const float *ba;
 } dcvc_dwc_args;
 int64_t dcvc_frag_pack_weights(const float *w, int rows, int k, void *out);
 int dcvc_dw_conv2_split(const dcvc_dwc_args *a, void *stream);
