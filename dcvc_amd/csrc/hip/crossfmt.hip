@@ -14,102 +14,20 @@
 //     frame as YUVWriter stores it.
 //
 // Every value is bit-equal to the reference's numpy / scipy result, so the
-// colour arithmetic below is written operation by operation in numpy's order
-// with contraction into FMAs switched off (numpy rounds after every ufunc).
-#include "frame.h"
+// colour arithmetic (crossfmt.h, shared with frame16.hip) is written operation
+// by operation in numpy's order with contraction into FMAs switched off (numpy
+// rounds after every ufunc).
+#include "crossfmt.h"
 
 namespace {
 
-// ITU-R BT.709 (functional.py:10-13).  numpy multiplies float32 arrays by
-// these Python doubles as float32 scalars: each constant is the double
-// expression rounded once to fp32.
-constexpr float KR = (float)0.2126, KG = (float)0.7152, KB = (float)0.0722;
-constexpr float C_CR = (float)(2.0 - 2.0 * 0.2126), C_CB = (float)(2.0 - 2.0 * 0.0722);
-constexpr float D_CB = (float)(1.0 - 0.0722), D_CR = (float)(1.0 - 0.2126);
-
-// r = y + (2 - 2 Kr) (cr - 0.5); b = y + (2 - 2 Kb) (cb - 0.5);
-// g = (y - Kr r - Kb b) / Kg; clip (functional.py:52-57)
-__device__ __forceinline__ void ycc_to_rgb(float y, float cb, float cr, float &r, float &g, float &b) {
-#pragma clang fp contract(off)
-  const float tr = cr - 0.5f, tb = cb - 0.5f;
-  const float pr = C_CR * tr, pb = C_CB * tb;
-  const float rr = y + pr, bb = y + pb;
-  const float m1 = KR * rr, m2 = KB * bb;
-  const float d1 = y - m1;
-  const float d2 = d1 - m2;
-  r = clamp01(rr);
-  g = clamp01(d2 / KG);
-  b = clamp01(bb);
-}
-
-// y = Kr r + Kg g + Kb b; cb = 0.5 (b - y) / (1 - Kb) + 0.5;
-// cr = 0.5 (r - y) / (1 - Kr) + 0.5, unclipped (functional.py:25-29)
-__device__ __forceinline__ void rgb_to_ycc(float r, float g, float b, float &y, float &cb, float &cr) {
-#pragma clang fp contract(off)
-  const float m0 = KR * r, m1 = KG * g, m2 = KB * b;
-  const float s0 = m0 + m1;
-  y = s0 + m2;
-  const float db = b - y, dr = r - y;
-  const float hb = 0.5f * db, hr = 0.5f * dr;
-  const float qb = hb / D_CB, qr = hr / D_CR;
-  cb = qb + 0.5f;
-  cr = qr + 0.5f;
-}
-
-// float32 mean of a 2x2 block as numpy's mean(axis=(-1, -3)) forms it:
-// (x00 + x01) + (x10 + x11) (sse_yuv420_kernel, frame.hip), except for a
-// chroma plane one column wide (seq), whose four values numpy reduces as one
-// contiguous run, ((x00 + x01) + x10) + x11
-__device__ __forceinline__ float mean4(float x00, float x01, float x10, float x11, bool seq) {
-  const float s = seq ? ((x00 + x01) + x10) + x11 : (x00 + x01) + (x10 + x11);
-  return s / 4.f;
-}
-
-// scipy.ndimage.zoom(order=1) along one axis of length n doubled to 2n: output
-// index i samples at cc = i * z, z = (n - 1) / (2n - 1) formed first in double
-// (on the host: zoom_ratio); taps floor(cc) and floor(cc) + 1.  scipy weighs
-// a tap k by 1 - |k - cc|: w0 = 1 - f and w1 = 1 - w0, which is not always f
-// in the last double bit, and that bit decides fp32 ties such as (2a + b) / 3.
-// n = 1: z = 0, both outputs take tap 0.
-struct Tap {
-  int i0, i1;
-  double w0, w1;
-};
-
-__device__ __forceinline__ Tap zoom1_tap(int i, int n, double z) {
-#pragma clang fp contract(off)
-  const double cc = (double)i * z;
-  const double fl = floor(cc);
-  const double f = cc - fl;
-  const int i0 = max((int)fl, 0);
-  Tap t;
-  t.i0 = min(i0, n - 1);
-  t.i1 = min(i0 + 1, n - 1);
-  t.w0 = 1.0 - f;
-  t.w1 = 1.0 - t.w0;
-  return t;
-}
-
-// the four products (v * w_row) * w_col summed in double in scipy's order
-// (r0, c0), (r0, c1), (r1, c0), (r1, c1), rounded once to fp32
-__device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v11, const Tap &tr, const Tap &tc) {
-#pragma clang fp contract(off)
-  const double p00 = ((double)v00 * tr.w0) * tc.w0;
-  const double p01 = ((double)v01 * tr.w0) * tc.w1;
-  const double p10 = ((double)v10 * tr.w1) * tc.w0;
-  const double p11 = ((double)v11 * tr.w1) * tc.w1;
-  double t = p00;
-  t = t + p01;
-  t = t + p10;
-  t = t + p11;
-  return (float)t;
-}
-
 // dcvc_yuv420_to_rgb_nhwc: one thread per pixel of the padded output; a
 // padding pixel recomputes its edge pixel (F.pad replicate, test_video.py:
-// 130-135).  rgb_planes (3 x h x w) receives the crop.
-__global__ void yuv420_rgb_kernel(const uint8_t *__restrict__ ysrc, const uint8_t *__restrict__ uvsrc, int h, int w,
-                                  double zy, double zx, FView out, float *__restrict__ rgb_planes) {
+// 130-135).  rgb_planes (3 x h x w) receives the crop.  S: uint8 samples
+// (x / 255) or fp32 planes already in [0, 1] (smp, crossfmt.h).
+template <typename S>
+__global__ void yuv420_rgb_kernel(const S *__restrict__ ysrc, const S *__restrict__ uvsrc, int h, int w, double zy,
+                                  double zx, FView out, float *__restrict__ rgb_planes) {
   const int64_t n = (int64_t)out.H * out.W;
   const int hh = h / 2, hw = w / 2;
   const int64_t cplane = (int64_t)hh * hw, plane = (int64_t)h * w;
@@ -119,10 +37,10 @@ __global__ void yuv420_rgb_kernel(const uint8_t *__restrict__ ysrc, const uint8_
     const Tap tr = zoom1_tap(sy, hh, zy), tc = zoom1_tap(sx, hw, zx);
     const int64_t o00 = (int64_t)tr.i0 * hw + tc.i0, o01 = (int64_t)tr.i0 * hw + tc.i1;
     const int64_t o10 = (int64_t)tr.i1 * hw + tc.i0, o11 = (int64_t)tr.i1 * hw + tc.i1;
-    const float yv = u8f(ysrc[(int64_t)sy * w + sx]);
-    const float cb = bilerp(u8f(uvsrc[o00]), u8f(uvsrc[o01]), u8f(uvsrc[o10]), u8f(uvsrc[o11]), tr, tc);
-    const float cr = bilerp(u8f(uvsrc[cplane + o00]), u8f(uvsrc[cplane + o01]), u8f(uvsrc[cplane + o10]),
-                            u8f(uvsrc[cplane + o11]), tr, tc);
+    const float yv = smp(ysrc[(int64_t)sy * w + sx]);
+    const float cb = bilerp(smp(uvsrc[o00]), smp(uvsrc[o01]), smp(uvsrc[o10]), smp(uvsrc[o11]), tr, tc);
+    const float cr = bilerp(smp(uvsrc[cplane + o00]), smp(uvsrc[cplane + o01]), smp(uvsrc[cplane + o10]),
+                            smp(uvsrc[cplane + o11]), tr, tc);
     float r, g, b;
     ycc_to_rgb(yv, cb, cr, r, g, b);
     float *o = out.p + pix * out.cs + out.co;
@@ -138,10 +56,12 @@ __global__ void yuv420_rgb_kernel(const uint8_t *__restrict__ ysrc, const uint8_
   }
 }
 
-// dcvc_rgb_to_yuv420_planes: one thread per 2x2 block of the uint8 CHW frame;
+// dcvc_rgb_to_yuv420_planes: one thread per 2x2 block of the CHW frame
+// (uint8, or fp32 for dcvc_rgbf_to_yuv420_planes);
 // rgb_to_ycbcr420 (functional.py:16-39): Y of the four pixels and the block's
 // Cb, Cr means, clipped after the mean
-__global__ void rgb_yuv420_planes_kernel(const uint8_t *__restrict__ src, int h, int w, float *__restrict__ yp,
+template <typename S>
+__global__ void rgb_yuv420_planes_kernel(const S *__restrict__ src, int h, int w, float *__restrict__ yp,
                                          float *__restrict__ uvp) {
   const int hh = h / 2, hw = w / 2;
   const int64_t n = (int64_t)hh * hw, plane = (int64_t)h * w;
@@ -154,7 +74,7 @@ __global__ void rgb_yuv420_planes_kernel(const uint8_t *__restrict__ src, int h,
       for (int dx = 0; dx < 2; ++dx) {
         const int64_t q = (int64_t)(2 * by + dy) * w + 2 * bx + dx;
         float y;
-        rgb_to_ycc(u8f(src[q]), u8f(src[plane + q]), u8f(src[2 * plane + q]), y, cb[dy][dx], cr[dy][dx]);
+        rgb_to_ycc(smp(src[q]), smp(src[plane + q]), smp(src[2 * plane + q]), y, cb[dy][dx], cr[dy][dx]);
         yp[q] = clamp01(y);
       }
     uvp[blk] = clamp01(mean4(cb[0][0], cb[0][1], cb[1][0], cb[1][1], hw == 1));
@@ -298,13 +218,7 @@ __global__ void rgb_planes_f32_kernel(FView xh, const float *__restrict__ src, i
 // the crop (Y clipped; U, V = clipped 2x2 means of the values as given, as
 // recon_yuv_u8_kernel), ycbcr420_to_rgb(order=1), clip(rint(v * 255)) as HWC
 // uint8.  One thread per crop pixel, recomputing the four block means per
-// chroma plane its taps need.
-__device__ __forceinline__ float block_mean(const FView &xh, int by, int bx, int c, bool seq) {
-  const float *p0 = xh.p + ((int64_t)(2 * by) * xh.W + 2 * bx) * xh.cs + xh.co + c;
-  const float *p1 = p0 + (int64_t)xh.W * xh.cs;
-  return clamp01(mean4(p0[0], p0[xh.cs], p1[0], p1[xh.cs], seq));
-}
-
+// chroma plane its taps need (block_mean, crossfmt.h).
 __global__ void recon_yuv_rgb_u8_kernel(FView xh, int h, int w, double zy, double zx, uint8_t *__restrict__ out) {
   const int64_t n = (int64_t)h * w;
   const int hh = h / 2, hw = w / 2;
@@ -347,19 +261,6 @@ __global__ void recon_rgb_yuv_u8_kernel(FView xh, int h, int w, uint8_t *__restr
   }
 }
 
-// (n - 1) / (2n - 1), the ratio scipy's zoom forms before it multiplies
-double zoom_ratio(int n) { return n > 1 ? (double)(n - 1) / (double)(2 * n - 1) : 0.0; }
-
-constexpr int CF_BLOCK = 256;
-constexpr int64_t CF_MAX_BLOCKS = 65536;
-
-unsigned cf_blocks(int64_t n) {
-  const int64_t g = (n + CF_BLOCK - 1) / CF_BLOCK;
-  return (unsigned)(g < CF_MAX_BLOCKS ? (g > 0 ? g : 1) : CF_MAX_BLOCKS);
-}
-
-bool even_frame(int h, int w) { return h >= 2 && w >= 2 && !(h & 1) && !(w & 1); }
-
 }  // namespace
 
 extern "C" int dcvc_yuv420_to_rgb_nhwc(const uint8_t *y, const uint8_t *uv, int h, int w, dcvc_tensor out,
@@ -368,8 +269,31 @@ extern "C" int dcvc_yuv420_to_rgb_nhwc(const uint8_t *y, const uint8_t *uv, int 
     return DCVC_HIP_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)out.H * out.W;
-  hipLaunchKernelGGL(yuv420_rgb_kernel, dim3(cf_blocks(n)), dim3(CF_BLOCK), 0, st, y, uv, h, w, zoom_ratio(h / 2),
-                     zoom_ratio(w / 2), fv(out), rgb_planes);
+  hipLaunchKernelGGL(yuv420_rgb_kernel<uint8_t>, dim3(cf_blocks(n)), dim3(CF_BLOCK), 0, st, y, uv, h, w,
+                     zoom_ratio(h / 2), zoom_ratio(w / 2), fv(out), rgb_planes);
+  DCVC_LAUNCH_CHECK();
+  return DCVC_HIP_OK;
+}
+
+extern "C" int dcvc_yuv420f_to_rgb_nhwc(const float *y, const float *uv, int h, int w, float *out, int H, int W,
+                                        int cstride, int coff, float *rgb_planes, void *stream) {
+  if (!y || !uv || !rgb_planes || !view_ok(out, H, W, cstride, coff) || !even_frame(h, w) || H < h || W < w)
+    return DCVC_HIP_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n = (int64_t)H * W;
+  hipLaunchKernelGGL(yuv420_rgb_kernel<float>, dim3(cf_blocks(n)), dim3(CF_BLOCK), 0, st, y, uv, h, w,
+                     zoom_ratio(h / 2), zoom_ratio(w / 2), fvs(out, H, W, cstride, coff), rgb_planes);
+  DCVC_LAUNCH_CHECK();
+  return DCVC_HIP_OK;
+}
+
+extern "C" int dcvc_rgbf_to_yuv420_planes(const float *rgb, int h, int w, float *y_plane, float *uv_planes,
+                                          void *stream) {
+  if (!rgb || !y_plane || !uv_planes || !even_frame(h, w)) return DCVC_HIP_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t n = (int64_t)(h / 2) * (w / 2);
+  hipLaunchKernelGGL(rgb_yuv420_planes_kernel<float>, dim3(cf_blocks(n)), dim3(CF_BLOCK), 0, st, rgb, h, w, y_plane,
+                     uv_planes);
   DCVC_LAUNCH_CHECK();
   return DCVC_HIP_OK;
 }
@@ -379,7 +303,7 @@ extern "C" int dcvc_rgb_to_yuv420_planes(const uint8_t *rgb, int h, int w, float
   if (!rgb || !y_plane || !uv_planes || !even_frame(h, w)) return DCVC_HIP_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)(h / 2) * (w / 2);
-  hipLaunchKernelGGL(rgb_yuv420_planes_kernel, dim3(cf_blocks(n)), dim3(CF_BLOCK), 0, st, rgb, h, w, y_plane,
+  hipLaunchKernelGGL(rgb_yuv420_planes_kernel<uint8_t>, dim3(cf_blocks(n)), dim3(CF_BLOCK), 0, st, rgb, h, w, y_plane,
                      uv_planes);
   DCVC_LAUNCH_CHECK();
   return DCVC_HIP_OK;

@@ -85,6 +85,14 @@ inline bool frame_ok(const dcvc_tensor &t) {
 
 inline FView fv(const dcvc_tensor &t) { return FView{reinterpret_cast<float *>(t.ptr), t.H, t.W, t.cstride, t.coff}; }
 
+// The same 3-channel fp32 frame view handed over as scalars (the entry points
+// of the 9..16-bit sources): base pointer, H, W, channel stride and offset.
+inline bool view_ok(const float *p, int H, int W, int cs, int co) {
+  return p && H > 0 && W > 0 && co >= 0 && co + 3 <= cs;
+}
+
+inline FView fvs(const float *p, int H, int W, int cs, int co) { return FView{const_cast<float *>(p), H, W, cs, co}; }
+
 inline unsigned sse_blocks(int64_t n) {
   const int64_t g = (n + SSE_BLOCK - 1) / SSE_BLOCK;
   return (unsigned)(g < SSE_MAX_BLOCKS ? (g > 0 ? g : 1) : SSE_MAX_BLOCKS);

@@ -27,6 +27,13 @@ msssim.hip), pinned to the reference's outputs.  RGB MS-SSIM is
 ``pytorch_msssim.ms_ssim`` in the reference (DC and HEM), a package absent
 from this image: ``MsSsimRGB`` follows its published algorithm on the GPU and
 the log carries ``msssim_unpinned``.
+
+High bit depth: raw planar .rgb (``RGBReader``, the reference's) and YUV420
+files of 9..16 bits per sample hand over uint16 frames, which cross to the GPU
+as they are; a sample is x / ((1 << d) - 1).  A source of the codec's format is
+read by the 16-bit kernels directly (frame16.hip), the cross-format ingest and
+MS-SSIM go through fp32 planes, and ``ReconWriter`` stores uint16 out.yuv /
+out.rgb.  8 bits is the uint8 code, unchanged.
 """
 import contextlib
 import os
@@ -40,21 +47,38 @@ from .stream_helper import get_padding_size
 
 
 # ----------------------------------------------------------------- readers
-class YUVReader:
-    """Raw 8-bit YUV420 file reader (DCVC-DC/src/utils/video_reader.py:
-    121-161).  ``read_one_frame`` returns uint8 ``(y (h, w), uv (2, h/2,
-    w/2))``, or ``(None, None)`` at the end of the file, whatever
-    ``dst_format`` the codec wants; the reference's float conversion (x / 255)
-    and, for an RGB codec, its ycbcr420_to_rgb happen on the GPU (FrameStage)."""
+def _check_bit_depth(bit_depth):
+    if not isinstance(bit_depth, int) or isinstance(bit_depth, bool) or not 8 <= bit_depth <= 16:
+        raise ValueError(f"bit depth {bit_depth!r} is outside 8..16")
+    return bit_depth
 
-    def __init__(self, src_path, width, height, src_format="420", skip_frame=0):
+
+def _sample_dtype(bit_depth):
+    """uint8 at 8 bits, little-endian uint16 at 9..16 (video_reader.py:93-98)."""
+    return np.dtype(np.uint8) if _check_bit_depth(bit_depth) == 8 else np.dtype("<u2")
+
+
+class YUVReader:
+    """Raw YUV420 file reader (DCVC-DC/src/utils/video_reader.py:121-161).
+    ``read_one_frame`` returns uint8 ``(y (h, w), uv (2, h/2, w/2))``, or
+    ``(None, None)`` at the end of the file, whatever ``dst_format`` the codec
+    wants; the reference's float conversion (x / 255) and, for an RGB codec,
+    its ycbcr420_to_rgb happen on the GPU (FrameStage).  ``bit_depth`` 9..16
+    (beyond the reference, whose YUVReader is 8-bit): little-endian uint16
+    samples, full range like the 8-bit rule, returned as uint16 planes; frame
+    and skip sizes double."""
+
+    def __init__(self, src_path, width, height, src_format="420", skip_frame=0, bit_depth=8):
         if src_format != "420":
             raise ValueError("only 420 sources are supported (video_reader.py:127)")
+        if _check_bit_depth(bit_depth) > 8 and (width % 2 or height % 2):
+            raise ValueError(f"a 4:2:0 file needs even sizes, not {width} x {height}")
         if not src_path.endswith(".yuv"):
             src_path = src_path + ".yuv"
         self.src_path, self.width, self.height = src_path, width, height
-        self.y_size = width * height
-        self.uv_size = width * height // 2
+        self.bit_depth, self.dtype = bit_depth, _sample_dtype(bit_depth)
+        self.y_size = width * height * self.dtype.itemsize
+        self.uv_size = width * height // 2 * self.dtype.itemsize
         self.eof = False
         self.file = open(src_path, "rb")  # noqa: SIM115 (closed in close())
         for _ in range(skip_frame):
@@ -77,9 +101,43 @@ class YUVReader:
         r = self._read()
         if r is None:
             return None, None
-        y = np.frombuffer(r[0], dtype=np.uint8).reshape(self.height, self.width)
-        uv = np.frombuffer(r[1], dtype=np.uint8).reshape(2, self.height // 2, self.width // 2)
+        y = np.frombuffer(r[0], dtype=self.dtype).reshape(self.height, self.width)
+        uv = np.frombuffer(r[1], dtype=self.dtype).reshape(2, self.height // 2, self.width // 2)
         return y, uv
+
+    def close(self):
+        self.file.close()
+
+
+class RGBReader:
+    """Raw planar RGB file reader (video_reader.py:83-118): 3 x h x w samples
+    per frame, uint8 or, at ``bit_depth`` 9..16, little-endian uint16; ".rgb"
+    is appended to a path that lacks it.  ``read_one_frame`` returns the CHW
+    frame in its native type, or None at the end of the file (a last frame
+    that is cut short counts as the end); the reference's float conversion
+    (x / max_val) and, for a YUV420 codec, its rgb_to_ycbcr420 happen on the
+    GPU (FrameStage)."""
+
+    def __init__(self, src_path, width, height, bit_depth=8):
+        if not src_path.endswith(".rgb"):
+            src_path = src_path + ".rgb"
+        self.src_path, self.width, self.height = src_path, width, height
+        self.bit_depth, self.dtype = bit_depth, _sample_dtype(bit_depth)
+        self.max_val = (1 << bit_depth) - 1
+        self.rgb_size = width * height * 3 * self.dtype.itemsize
+        self.eof = False
+        self.file = open(src_path, "rb")  # noqa: SIM115 (closed in close())
+
+    def read_one_frame(self, dst_format="rgb"):
+        if dst_format not in ("rgb", "420"):
+            raise ValueError(f"unknown dst_format {dst_format!r}")
+        if self.eof:
+            return None
+        rgb = self.file.read(self.rgb_size)
+        if len(rgb) < self.rgb_size:
+            self.eof = True
+            return None
+        return np.frombuffer(rgb, dtype=self.dtype).reshape(3, self.height, self.width)
 
     def close(self):
         self.file.close()
@@ -124,7 +182,8 @@ class PNGReader:
 
 class ArrayReader:
     """In-memory frames (synthetic sequences, tests): uint8 CHW RGB arrays,
-    or (y, uv) uint8 plane pairs for YUV420."""
+    or (y, uv) uint8 plane pairs for YUV420; uint16 arrays for a 9..16-bit
+    source (FrameStage's ``bit_depth`` says how many bits they hold)."""
 
     def __init__(self, frames):
         self.frames = list(frames)
@@ -150,17 +209,28 @@ class FrameStage:
     to the codec's own format (``yuv420``).  When it differs, ``load`` converts
     the frame on the GPU and keeps the converted fp32 source planes
     (``src_f32``: (rgb 3 x h x w,) or (y, uv)) for ``distortion`` and MS-SSIM:
-    the frame the reference's reader would have returned."""
+    the frame the reference's reader would have returned.
 
-    def __init__(self, h, w, align, yuv420, zero_pad, frame_num, device, src_format=None):
+    ``bit_depth`` 9..16: the frames are uint16 (x / ((1 << bit_depth) - 1)),
+    uploaded as they are.  A source of the codec's format is read directly by
+    the 16-bit kernels (frame16.hip); one of the other format is first turned
+    into fp32 planes (``dcvc_u16_to_f32``) and then converted as above.  8 is
+    the uint8 code, untouched."""
+
+    def __init__(self, h, w, align, yuv420, zero_pad, frame_num, device, src_format=None, bit_depth=8):
         self.h, self.w, self.yuv, self.zero_pad = h, w, yuv420, zero_pad
         codec_format = "420" if yuv420 else "rgb"
         src_format = codec_format if src_format is None else src_format
         if src_format not in ("rgb", "420"):
             raise ValueError(f"unknown src_format {src_format!r}")
+        self.bit_depth = _check_bit_depth(bit_depth)
+        self.deep = bit_depth > 8
         self.src_yuv = src_format == "420"
+        if self.deep and (self.src_yuv or yuv420) and (h % 2 or w % 2):
+            raise ValueError(f"4:2:0 needs even sizes, not {w} x {h}")
         self.cross = src_format != codec_format
         self.src_f32 = None
+        self.raw_f32 = None       # bit_depth > 8: the uint16 source as fp32 planes (cross ingest, MS-SSIM)
         if self.cross:
             if zero_pad or h % 2 or w % 2:
                 raise ValueError("a converted source needs even sizes and replicate padding")
@@ -176,17 +246,47 @@ class FrameStage:
         self.ws = K.frame_sse_workspace(device)
         self.sse = torch.zeros((max(frame_num, 1), 3), dtype=torch.float64, device=device)
 
+    def _up(self, a, key):
+        if self.deep:
+            a = np.asarray(a)
+            if a.dtype != np.uint16:
+                raise ValueError(f"a {self.bit_depth}-bit source hands over uint16 frames, not {a.dtype}")
+            a = a.view(np.int16)          # the same bits: torch moves int16 on every build
+        return K.upload(a, self.dev, key)
+
     def upload(self, frame):
-        """Host uint8 frame (CHW RGB, or (y, uv)) -> device tensors."""
+        """Host frame (CHW RGB, or (y, uv); uint8, or uint16 above 8 bits) ->
+        device tensors."""
         if self.src_yuv:
             y, uv = frame
-            return K.upload(y, self.dev, "frame_y"), K.upload(uv, self.dev, "frame_uv")
-        return K.upload(frame, self.dev, "frame")
+            return self._up(y, "frame_y"), self._up(uv, "frame_uv")
+        return self._up(frame, "frame")
+
+    def _raw_f32(self, dframe):
+        """The 16-bit source as fp32 planes x / max_val in its own layout."""
+        h, w = self.h, self.w
+        if self.raw_f32 is None:
+            shapes = ((h, w), (2, h // 2, w // 2)) if self.src_yuv else ((3, h, w),)
+            self.raw_f32 = tuple(torch.empty(s, dtype=torch.float32, device=self.dev) for s in shapes)
+        for src, dst in zip(dframe if self.src_yuv else (dframe,), self.raw_f32):
+            K.u16_to_f32(src, self.bit_depth, dst)
+        return self.raw_f32
+
+    def source_f32(self, dframe):
+        """The fp32 source planes MS-SSIM compares against ((rgb,) or (y, uv)
+        in the codec's format), or None for an 8-bit source of the codec's own
+        format (whose uint8 planes the metrics read directly).  After ``load``
+        of the same frame."""
+        if self.cross:
+            return self.src_f32
+        return self._raw_f32(dframe) if self.deep else None
 
     def load(self, dframe):
-        """Device uint8 frame -> padded NHWC fp32 codec input (test_video.py:
+        """Device source frame -> padded NHWC fp32 codec input (test_video.py:
         108-132: ycbcr420_to_444(order=0) for YUV, x / 255, F.pad; for a source
         of the other format, the reader's conversion first)."""
+        if self.deep:
+            return self._load16(dframe)
         if self.cross and self.yuv:
             K.rgb_to_yuv420_planes(dframe, self.h, self.w, *self.src_f32)
             K.yuv420f_to_nhwc(self.src_f32[0], self.src_f32[1], self.h, self.w, self.x)
@@ -198,6 +298,20 @@ class FrameStage:
             K.frame_to_nhwc(dframe, self.h, self.w, self.x, zero_pad=self.zero_pad)
         return self.x
 
+    def _load16(self, dframe):
+        h, w, d = self.h, self.w, self.bit_depth
+        if self.cross and self.yuv:
+            K.rgbf_to_yuv420_planes(self._raw_f32(dframe)[0], h, w, *self.src_f32)
+            K.yuv420f_to_nhwc(self.src_f32[0], self.src_f32[1], h, w, self.x)
+        elif self.cross:
+            yf, uvf = self._raw_f32(dframe)
+            K.yuv420f_to_rgb_nhwc(yf, uvf, h, w, self.x, self.src_f32[0])
+        elif self.yuv:
+            K.yuv420p16_to_nhwc(dframe[0], dframe[1], h, w, d, self.x)
+        else:
+            K.frame16_to_nhwc(dframe, h, w, d, self.x, zero_pad=self.zero_pad)
+        return self.x
+
     def distortion(self, recon, dframe, slot):
         """recon_frame.clamp_(0, 1), crop, and the squared-error sums of the
         frame into row ``slot`` (test_video.py:169-195)."""
@@ -207,6 +321,10 @@ class FrameStage:
             K.frame_sse_f32(r, self.src_f32[0], self.h, self.w, self.ws, self.sse[slot], uv_f32=self.src_f32[1])
         elif self.cross:
             K.frame_sse_f32(r, self.src_f32[0], self.h, self.w, self.ws, self.sse[slot])
+        elif self.deep and self.yuv:
+            K.frame16_sse(r, dframe[0], self.h, self.w, self.bit_depth, self.ws, self.sse[slot], uv_u16=dframe[1])
+        elif self.deep:
+            K.frame16_sse(r, dframe, self.h, self.w, self.bit_depth, self.ws, self.sse[slot])
         elif self.yuv:
             K.frame_sse(r, dframe[0], self.h, self.w, self.ws, self.sse[slot], uv_u8=dframe[1])
         else:
@@ -353,34 +471,53 @@ class ReconWriter:
     The decoded frame is quantised on the GPU (dcvc_recon_to_u8: the crop,
     clip(rint(v * 255)), and for YUV the ycbcr444_to_420 chroma means), copied
     once to pinned memory, and written by one background thread in frame order
-    so file encoding overlaps the next frame.  kind: "png" | "yuv" | "hem_png";
+    so file encoding overlaps the next frame.  kind: "png" | "yuv" | "hem_png" |
+    "rgb" (RGBWriter's raw planar out.rgb, video_writer.py:50-80);
     src_format "rgb" | "420" (what the codec's frames hold, dist_in_yuv420).
+    ``bit_depth`` 9..16: "yuv" and "rgb" store little-endian uint16 samples,
+    clip(rint(v * max_val)) on the GPU (dcvc_recon_to_u16 / _cross); PNG output
+    stays 8-bit.
     The reference's cross cases (a 4:2:0 frame into PNGWriter, an RGB frame into
     YUVWriter, functional.py:16-58) are converted and quantised on the GPU as
     well (dcvc_recon_to_u8_cross) and take the same pinned-copy path."""
 
-    def __init__(self, path, h, w, kind, src_format, device):
+    def __init__(self, path, h, w, kind, src_format, device, bit_depth=8):
         from concurrent.futures import ThreadPoolExecutor
+        if kind not in ("png", "yuv", "hem_png", "rgb"):
+            raise ValueError(f"unknown writer kind {kind!r}")
+        self.bit_depth = _check_bit_depth(bit_depth)
+        self.deep = bit_depth > 8
+        if self.deep and kind in ("png", "hem_png"):
+            raise ValueError(f"PNG output is 8-bit; write {bit_depth}-bit frames as 'rgb' or 'yuv'")
+        if self.deep and (kind == "yuv" or src_format == "420") and (h % 2 or w % 2):
+            raise ValueError(f"4:2:0 needs even sizes, not {w} x {h}")
         os.makedirs(path, exist_ok=True)
         self.path, self.h, self.w, self.kind, self.fmt = path, h, w, kind, src_format
         self.yuv_out = kind == "yuv"
         self.quant_yuv = src_format == "420"
         self.cross = self.quant_yuv != self.yuv_out
         self.n = h * w + 2 * (h // 2) * (w // 2) if self.yuv_out else 3 * h * w
-        self.dev_buf = torch.empty(self.n, dtype=torch.uint8, device=device)
+        self.dtype = torch.int16 if self.deep else torch.uint8      # uint16 bits travel as int16
+        self.dev_buf = torch.empty(self.n, dtype=self.dtype, device=device)
         self.pool = ThreadPoolExecutor(1)
         self.jobs = []
         self.index = 1                              # PNGWriter.current_frame_index starts at 1
-        self.file = open(os.path.join(path, "out.yuv"), "wb") if self.yuv_out else None
+        self.file = None
+        if kind in ("yuv", "rgb"):                  # YUVWriter / RGBWriter: out.yuv / out.rgb in the folder
+            self.file = open(os.path.join(path, "out." + kind), "wb")  # noqa: SIM115 (closed in close())
 
     def write(self, recon, frame_idx):
         from .dc.video_model import as_act
         x = as_act(recon)
-        if self.cross:
+        if self.deep and self.cross:
+            K.recon_to_u16_cross(x, self.h, self.w, self.bit_depth, not self.yuv_out, self.dev_buf)
+        elif self.deep:
+            K.recon_to_u16(x, self.h, self.w, self.bit_depth, self.quant_yuv, self.dev_buf)
+        elif self.cross:
             K.recon_to_u8_cross(x, self.h, self.w, not self.yuv_out, self.dev_buf)
         else:
             K.recon_to_u8(x, self.h, self.w, self.quant_yuv, self.dev_buf)
-        host = torch.empty(self.n, dtype=torch.uint8, pin_memory=True)
+        host = torch.empty(self.n, dtype=self.dtype, pin_memory=True)
         host.copy_(self.dev_buf, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -394,6 +531,11 @@ class ReconWriter:
         h, w = self.h, self.w
         if self.yuv_out:
             self.file.write(a.tobytes())            # Y plane then U, V planes (YUVWriter)
+            return
+        if self.kind == "rgb":                      # RGBWriter: planar 3 x h x w
+            if not self.deep:                       # the uint8 kernels quantise into h x w x 3
+                a = np.ascontiguousarray(a.reshape(h, w, 3).transpose(2, 0, 1))
+            self.file.write(a.tobytes())
             return
         from PIL import Image
         Image.fromarray(a.reshape(h, w, 3)).save(os.path.join(self.path, name))
@@ -511,17 +653,49 @@ def generate_log_json(frame_num, frame_pixel_num, test_time, frame_types, bits, 
 def _reader(args, yuv):
     if "src_reader" in args:
         return args["src_reader"]
+    depth = args.get("src_bit_depth", 8)
     if args["src_type"] == "yuv420":
-        return YUVReader(args["src_path"], args["src_width"], args["src_height"])
+        return YUVReader(args["src_path"], args["src_width"], args["src_height"], bit_depth=depth)
+    if args["src_type"] == "rgb":
+        return RGBReader(args["src_path"], args["src_width"], args["src_height"], bit_depth=depth)
     if args["src_type"] == "png":
+        if depth != 8:
+            raise ValueError(f"PNG sources are 8-bit (src_bit_depth {depth})")
         return PNGReader(args.get("src_path", args.get("img_path")), args["src_width"], args["src_height"])
     raise ValueError(f"unknown src_type {args['src_type']!r}")
+
+
+def _src_format(src_type, codec_fmt):
+    """"rgb" | "420": what a source of ``src_type`` ('png' | 'rgb' | 'yuv420',
+    None: the codec's own format) hands over."""
+    if src_type not in (None, "yuv420", "png", "rgb"):
+        raise ValueError(f"unknown src_type {src_type!r}")
+    return codec_fmt if src_type is None else ("420" if src_type == "yuv420" else "rgb")
+
+
+def _bit_depths(args, default=8):
+    """(src_bit_depth, recon_bit_depth) of ``args``: the source's depth
+    (``default`` when not given) and the decoded-frame files' (the source's
+    when not given)."""
+    src = _check_bit_depth(args.get("src_bit_depth", default))
+    return src, _check_bit_depth(args.get("recon_bit_depth", src))
+
+
+def _writer_kind(src_type, src_fmt, bit_depth):
+    """The decoded-frame writer that goes with a source: out.yuv for a YUV420
+    source, out.rgb for a raw RGB one (and for any RGB source above 8 bits,
+    which a PNG cannot hold), PNG files otherwise."""
+    if src_fmt != "rgb":
+        return "yuv"
+    return "rgb" if src_type == "rgb" or (src_type is None and bit_depth > 8) else "png"
 
 
 def run_test(p_frame_net, i_frame_net, args):
     """DCVC-DC/test_video.py:71-237 on the GPU codecs.  ``args`` takes the
     reference's keys (frame_num, gop_size, write_stream, bin_folder,
-    src_type 'png' | 'yuv420', src_path, src_width, src_height,
+    src_type 'png' | 'yuv420' | 'rgb' (a raw planar .rgb file), src_bit_depth
+    (8; 9..16 for uint16 .rgb / .yuv files), recon_bit_depth (the decoded-frame
+    files' depth, the source's by default), src_path, src_width, src_height,
     dist_in_yuv420, q_in_ckpt, i_frame_q_index, verbose, calc_ssim) plus an
     optional ``src_reader`` (an ArrayReader) in place of a file source.
     ``dist_in_yuv420`` selects the codec's format (YCbCr 4:4:4 input, as the
@@ -534,16 +708,17 @@ def run_test(p_frame_net, i_frame_net, args):
     yuv = bool(args.get("dist_in_yuv420", False))
     codec_fmt = "420" if yuv else "rgb"
     src_type = args.get("src_type")
-    if src_type not in (None, "yuv420", "png"):
-        raise ValueError(f"unknown src_type {src_type!r}")
-    src_fmt = codec_fmt if src_type is None else ("420" if src_type == "yuv420" else "rgb")
+    src_fmt = _src_format(src_type, codec_fmt)
+    src_depth, recon_depth = _bit_depths(args)
     device = i_frame_net.dev
     reader = _reader(args, yuv)
     h, w = args["src_height"], args["src_width"]
-    stage = FrameStage(h, w, 16, yuv, zero_pad=False, frame_num=frame_num, device=device, src_format=src_fmt)
+    stage = FrameStage(h, w, 16, yuv, zero_pad=False, frame_num=frame_num, device=device, src_format=src_fmt,
+                       bit_depth=src_depth)
     writer = None
     if args.get("save_decoded_frame"):   # test_video.py:84-88
-        writer = ReconWriter(args["recon_path"], h, w, "png" if src_fmt == "rgb" else "yuv", codec_fmt, device)
+        writer = ReconWriter(args["recon_path"], h, w, _writer_kind(src_type, src_fmt, recon_depth), codec_fmt,
+                             device, bit_depth=recon_depth)
     ms = None
     if args.get("calc_ssim"):
         ms = MsSsim(h, w, frame_num, device) if yuv else MsSsimRGB(h, w, frame_num, device)
@@ -581,8 +756,9 @@ def run_test(p_frame_net, i_frame_net, args):
             stage.distortion(recon, dframe, frame_idx)
             if ms is not None:
                 from .dc.video_model import as_act
-                if stage.cross:
-                    ms.run_f32(as_act(recon), *stage.src_f32, frame_idx)
+                src_f32 = stage.source_f32(dframe)
+                if src_f32 is not None:
+                    ms.run_f32(as_act(recon), *src_f32, frame_idx)
                 elif yuv:
                     ms.run(as_act(recon), dframe[0], dframe[1], frame_idx)
                 else:
@@ -633,17 +809,25 @@ def generate_log_json_hem(frame_num, frame_types, bits, psnrs, ssims, frame_pixe
 def run_test_hem(video_net, i_frame_net, args, device=None):
     """DCVC-HEM/test_video.py:80-172: PNG (or in-memory) RGB source, zero
     padding to a multiple of 64, q scales from ``args`` (i_frame_q_scale,
-    p_frame_mv_y_q_scale, p_frame_y_q_scale)."""
+    p_frame_mv_y_q_scale, p_frame_y_q_scale).  ``src_type`` 'rgb' reads a raw
+    planar .rgb file, ``src_bit_depth`` / ``recon_bit_depth`` as in
+    ``run_test``."""
     frame_num, gop_size = args["frame_num"], args["gop_size"]
     write_stream = bool(args.get("write_stream", False))
     device = device if device is not None else i_frame_net.dev
-    reader = _reader({**args, "src_type": args.get("src_type", "png")}, False)
+    src_type = args.get("src_type", "png")
+    if _src_format(src_type, "rgb") != "rgb":
+        raise ValueError("the HEM harness reads RGB sources")
+    src_depth, recon_depth = _bit_depths(args)
+    reader = _reader({**args, "src_type": src_type}, False)
     h, w = args["src_height"], args["src_width"]
-    stage = FrameStage(h, w, 64, False, zero_pad=True, frame_num=frame_num, device=device)
+    stage = FrameStage(h, w, 64, False, zero_pad=True, frame_num=frame_num, device=device, bit_depth=src_depth)
     ms = MsSsimRGB(h, w, frame_num, device) if min(h, w) > 160 else None  # HEM always reports ms_ssim (:150)
     writer = None
     if args.get("save_decoded_frame"):   # DCVC-HEM/test_video.py:161-163, 204-209
-        writer = ReconWriter(args["decoded_frame_folder"], h, w, "hem_png", "rgb", device)
+        # a raw RGB source (or any depth above 8 bits) gets RGBWriter's out.rgb in place of the PNG files
+        kind = "rgb" if src_type == "rgb" or recon_depth > 8 else "hem_png"
+        writer = ReconWriter(args["decoded_frame_folder"], h, w, kind, "rgb", device, bit_depth=recon_depth)
     frame_types, bits = [], []
     start_time = time.time()
     dpb = None
@@ -671,7 +855,11 @@ def run_test_hem(video_net, i_frame_net, args, device=None):
             stage.distortion(recon, dframe, frame_idx)
             if ms is not None:
                 from .dc.video_model import as_act
-                ms.run(as_act(recon), dframe, frame_idx)
+                src_f32 = stage.source_f32(dframe)
+                if src_f32 is not None:
+                    ms.run_f32(as_act(recon), *src_f32, frame_idx)
+                else:
+                    ms.run(as_act(recon), dframe, frame_idx)
             if writer is not None:
                 writer.write(recon, frame_idx)
     sse = stage.sums()
@@ -698,7 +886,8 @@ def encode_video(i_frame_net, p_frame_net, args):
     instead of ``encode_decode`` and a bin folder; ``args["digest"]`` (default
     True) stores the DPB digests.  Nothing is decoded: the log's bits are the
     frames' payload bits and its PSNR is that of the ENCODER's reconstruction
-    (which a decoder of the file reproduces bit for bit)."""
+    (which a decoder of the file reproduces bit for bit).  ``src_bit_depth``
+    above 8 is recorded in the file's header; the payloads do not depend on it."""
     from .sequence import SequenceEncoder, codec_of
     hem = codec_of(i_frame_net) == "HEM"
     _tag_format((i_frame_net, p_frame_net), args)
@@ -707,25 +896,25 @@ def encode_video(i_frame_net, p_frame_net, args):
     yuv = bool(args.get("dist_in_yuv420", False)) and not hem
     codec_fmt = "420" if yuv else "rgb"
     src_type = args.get("src_type")
-    if src_type not in (None, "yuv420", "png"):
-        raise ValueError(f"unknown src_type {src_type!r}")
-    src_fmt = codec_fmt if src_type is None else ("420" if src_type == "yuv420" else "rgb")
+    src_fmt = _src_format(src_type, codec_fmt)
     if hem and src_fmt != "rgb":
         raise ValueError("the HEM harness reads RGB sources")
+    src_depth, _ = _bit_depths(args)
     device = i_frame_net.dev
     reader = _reader({**args, "src_type": src_type or "png"} if hem else args, yuv)
     h, w = args["src_height"], args["src_width"]
     if hem:
-        stage = FrameStage(h, w, 64, False, zero_pad=True, frame_num=frame_num, device=device)
+        stage = FrameStage(h, w, 64, False, zero_pad=True, frame_num=frame_num, device=device, bit_depth=src_depth)
         q = dict(i_frame_q_scale=args["i_frame_q_scale"], p_frame_mv_y_q_scale=args["p_frame_mv_y_q_scale"],
                  p_frame_y_q_scale=args["p_frame_y_q_scale"])
     else:
-        stage = FrameStage(h, w, 16, yuv, zero_pad=False, frame_num=frame_num, device=device, src_format=src_fmt)
+        stage = FrameStage(h, w, 16, yuv, zero_pad=False, frame_num=frame_num, device=device, src_format=src_fmt,
+                           bit_depth=src_depth)
         q = dict(q_in_ckpt=args["q_in_ckpt"], q_index=args["i_frame_q_index"])
     frame_types, bits, fallbacks = [], [], []
     start_time = time.time()
     with SequenceEncoder(i_frame_net, p_frame_net, args["seq_path"], w, h, gop_size, yuv420=yuv,
-                         digest=bool(args.get("digest", True)), **q) as enc:
+                         digest=bool(args.get("digest", True)), bit_depth=src_depth, **q) as enc:
         for frame_idx in range(frame_num):
             frame = reader.read_one_frame(dst_format=src_fmt)
             if frame is None or (src_fmt == "420" and frame[0] is None):
@@ -762,8 +951,9 @@ def decode_video(i_frame_net, p_frame_net, args):
     ``sequence.SequenceDecoder`` (which verifies the stored DPB digests) and,
     with ``save_decoded_frame``, writes the frames as ``run_test`` /
     ``run_test_hem`` write them (``recon_path`` / ``decoded_frame_folder``;
-    ``src_type`` selects PNG or out.yuv as there, the codec's own format by
-    default).  Returns the per-frame bits and types."""
+    ``src_type`` selects PNG, out.rgb or out.yuv as there, the codec's own
+    format by default; ``recon_bit_depth``, by default the source depth the
+    file's header records).  Returns the per-frame bits and types."""
     from .sequence import SequenceDecoder, codec_of
     hem = codec_of(i_frame_net) == "HEM"
     _tag_format((i_frame_net, p_frame_net), args)
@@ -773,14 +963,17 @@ def decode_video(i_frame_net, p_frame_net, args):
         h, w = dec.height, dec.width
         codec_fmt = "420" if dec.reader.format == "yuv420" else "rgb"
         src_type = args.get("src_type")
-        src_fmt = codec_fmt if src_type is None else ("420" if src_type == "yuv420" else "rgb")
+        src_fmt = _src_format(src_type, codec_fmt)
+        _, depth = _bit_depths(args, default=dec.reader.bit_depth)   # the source's depth, from the header
         writer = None
         if args.get("save_decoded_frame"):
             if hem:
-                writer = ReconWriter(args["decoded_frame_folder"], h, w, "hem_png", "rgb", i_frame_net.dev)
+                kind = "rgb" if src_type == "rgb" or depth > 8 else "hem_png"
+                writer = ReconWriter(args["decoded_frame_folder"], h, w, kind, "rgb", i_frame_net.dev,
+                                     bit_depth=depth)
             else:
-                writer = ReconWriter(args["recon_path"], h, w, "png" if src_fmt == "rgb" else "yuv", codec_fmt,
-                                     i_frame_net.dev)
+                writer = ReconWriter(args["recon_path"], h, w, _writer_kind(src_type, src_fmt, depth), codec_fmt,
+                                     i_frame_net.dev, bit_depth=depth)
         with (writer if writer is not None else contextlib.nullcontext()):
             for frame_idx, out in enumerate(dec):
                 frame_types.append(0 if out["type"] == "I" else 1)
@@ -788,4 +981,4 @@ def decode_video(i_frame_net, p_frame_net, args):
                 if writer is not None:
                     writer.write(out["x_hat"], frame_idx)
     return {"frame_num": len(bits), "frame_pixel_num": h * w, "frame_type": frame_types, "frame_bits": bits,
-            "test_time": time.time() - start_time}
+            "bit_depth": depth, "test_time": time.time() - start_time}

@@ -106,6 +106,14 @@ HIP_SYMBOLS = [
     ("dcvc_yuv420f_to_nhwc", _i, [_vp, _vp, _i, _i, _T, _vp]),
     ("dcvc_frame_sse_f32", _i, [_T, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     ("dcvc_recon_to_u8_cross", _i, [_T, _i, _i, _i, _vp, _vp]),
+    ("dcvc_frame16_to_nhwc", _i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    ("dcvc_yuv420p16_to_nhwc", _i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    ("dcvc_frame16_sse", _i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    ("dcvc_recon_to_u16", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    ("dcvc_recon_to_u16_cross", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    ("dcvc_u16_to_f32", _i, [_vp, ctypes.c_int64, _i, _vp, _vp]),
+    ("dcvc_yuv420f_to_rgb_nhwc", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    ("dcvc_rgbf_to_yuv420_planes", _i, [_vp, _i, _i, _vp, _vp, _vp]),
     ("dcvc_quadtree_encode_step", _i, [_T, _T, _T, _i, _T, _T, _vp, _vp, _f, _f, _vp]),
     ("dcvc_quadtree_indexes_step", _i, [_T, _T, _i, _vp, _f, _f, _vp]),
     ("dcvc_quadtree_decode_step", _i, [_T, _T, _i, _vp, _T, _T, _vp]),
@@ -852,6 +860,102 @@ def recon_to_u8(x_hat, h, w, yuv420, out):
     assert out.dtype == torch.uint8 and out.numel() >= n and x_hat.dtype == F32 and x_hat.C == 3
     check(lib().dcvc_recon_to_u8(x_hat.c(), h, w, 1 if yuv420 else 0, out.data_ptr(), stream()), "recon_to_u8")
     return out
+
+
+# ---- 9..16-bit frames (frame16.hip): samples are 2-byte device tensors
+# (uint16, or the same bits as int16).  SCALAR_VIEW_SYMBOLS: the launchers
+# that take the NHWC frame as (base, H, W, cstride, coff) instead of a CTensor.
+SCALAR_VIEW_SYMBOLS = ("dcvc_frame16_to_nhwc", "dcvc_yuv420p16_to_nhwc", "dcvc_frame16_sse", "dcvc_recon_to_u16",
+                       "dcvc_recon_to_u16_cross", "dcvc_yuv420f_to_rgb_nhwc")
+
+
+def check_depth(bit_depth):
+    """A high-bit-depth path's depth: 9..16 (8 is the uint8 code's)."""
+    if not isinstance(bit_depth, int) or not 9 <= bit_depth <= 16:
+        raise ValueError(f"bit depth {bit_depth!r} is outside 9..16")
+    return bit_depth
+
+
+def _fv(a):
+    """An fp32 3-channel Act as the scalar view (base, H, W, cstride, coff)."""
+    assert a.dtype == F32 and a.C == 3
+    return a.buf.data_ptr(), a.H, a.W, a.buf.shape[2], a.coff
+
+
+def _s16(t, n):
+    assert t.element_size() == 2 and not t.dtype.is_floating_point and t.is_contiguous() and t.numel() == n, \
+        (t.dtype, t.numel(), n)
+    return t.data_ptr()
+
+
+def frame16_to_nhwc(src_u16, h, w, depth, y, zero_pad=False):
+    """16-bit CHW RGB device frame -> padded NHWC fp32 (dcvc_frame16_to_nhwc)."""
+    check(lib().dcvc_frame16_to_nhwc(_s16(src_u16, 3 * h * w), h, w, check_depth(depth), int(bool(zero_pad)), *_fv(y),
+                                     stream()), "frame16_to_nhwc")
+    return y
+
+
+def yuv420p16_to_nhwc(y_u16, uv_u16, h, w, depth, out):
+    """16-bit device planes Y and U|V -> padded NHWC YCbCr 4:4:4 fp32."""
+    check(lib().dcvc_yuv420p16_to_nhwc(_s16(y_u16, h * w), _s16(uv_u16, 2 * (h // 2) * (w // 2)), h, w,
+                                       check_depth(depth), *_fv(out), stream()), "yuv420p16_to_nhwc")
+    return out
+
+
+def frame16_sse(x_hat, src_u16, h, w, depth, workspace, out3, uv_u16=None):
+    """frame_sse against a 16-bit source (dcvc_frame16_sse)."""
+    assert out3.dtype == torch.float64 and out3.numel() >= 3
+    yuv = uv_u16 is not None
+    check(lib().dcvc_frame16_sse(*_fv(x_hat), _s16(src_u16, h * w if yuv else 3 * h * w),
+                                 _s16(uv_u16, 2 * (h // 2) * (w // 2)) if yuv else None, h, w, check_depth(depth),
+                                 int(yuv), workspace.data_ptr(), out3.data_ptr(), stream()), "frame16_sse")
+    return out3
+
+
+def recon_to_u16(x_hat, h, w, depth, yuv420, out):
+    """Decoded frame -> 16-bit samples (dcvc_recon_to_u16): planar 3 x h x w
+    RGB, or Y | U | V planes."""
+    n = h * w + 2 * (h // 2) * (w // 2) if yuv420 else 3 * h * w
+    check(lib().dcvc_recon_to_u16(*_fv(x_hat), h, w, check_depth(depth), 1 if yuv420 else 0, _s16(out, n), stream()),
+          "recon_to_u16")
+    return out
+
+
+def recon_to_u16_cross(x_hat, h, w, depth, to_rgb, out):
+    """recon_to_u8_cross as 16-bit samples (dcvc_recon_to_u16_cross)."""
+    n = 3 * h * w if to_rgb else h * w + 2 * (h // 2) * (w // 2)
+    check(lib().dcvc_recon_to_u16_cross(*_fv(x_hat), h, w, check_depth(depth), 1 if to_rgb else 0, _s16(out, n),
+                                        stream()), "recon_to_u16_cross")
+    return out
+
+
+def u16_to_f32(src_u16, depth, out_f32):
+    """16-bit samples -> fp32 sample / max_val, elementwise (dcvc_u16_to_f32)."""
+    assert out_f32.dtype == torch.float32 and out_f32.is_contiguous() and out_f32.numel() == src_u16.numel()
+    check(lib().dcvc_u16_to_f32(_s16(src_u16, src_u16.numel()), src_u16.numel(), check_depth(depth),
+                                out_f32.data_ptr(), stream()), "u16_to_f32")
+    return out_f32
+
+
+def yuv420f_to_rgb_nhwc(y_f32, uv_f32, h, w, out, rgb_planes):
+    """yuv420_to_rgb_nhwc on fp32 source planes (dcvc_yuv420f_to_rgb_nhwc)."""
+    assert y_f32.dtype == torch.float32 and uv_f32.dtype == torch.float32
+    assert y_f32.numel() == h * w and uv_f32.numel() == 2 * (h // 2) * (w // 2)
+    assert y_f32.is_contiguous() and uv_f32.is_contiguous()
+    assert rgb_planes.dtype == torch.float32 and rgb_planes.numel() == 3 * h * w and rgb_planes.is_contiguous()
+    check(lib().dcvc_yuv420f_to_rgb_nhwc(y_f32.data_ptr(), uv_f32.data_ptr(), h, w, *_fv(out), rgb_planes.data_ptr(),
+                                         stream()), "yuv420f_to_rgb_nhwc")
+    return out
+
+
+def rgbf_to_yuv420_planes(src_f32, h, w, y_f32, uv_f32):
+    """rgb_to_yuv420_planes on an fp32 CHW frame (dcvc_rgbf_to_yuv420_planes)."""
+    assert src_f32.dtype == torch.float32 and src_f32.numel() == 3 * h * w and src_f32.is_contiguous()
+    assert y_f32.dtype == torch.float32 and uv_f32.dtype == torch.float32
+    assert y_f32.numel() == h * w and uv_f32.numel() == 2 * (h // 2) * (w // 2)
+    assert y_f32.is_contiguous() and uv_f32.is_contiguous()
+    check(lib().dcvc_rgbf_to_yuv420_planes(src_f32.data_ptr(), h, w, y_f32.data_ptr(), uv_f32.data_ptr(), stream()),
+          "rgbf_to_yuv420_planes")
 
 
 def yuv_planes_f64(x_hat, y_u8, uv_u8, h, w, src, rec):

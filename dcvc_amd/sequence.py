@@ -25,7 +25,7 @@ CODECS = ("DC", "HEM")
 FORMATS = ("rgb", "yuv420")
 NOT_CLOSED = 0xFFFFFFFF
 FLAG_TWIN, FLAG_DIGEST = 1, 2
-_HEADER = struct.Struct("<8sBB16sHIII")     # magic, codec, format, precision, reserved, width, height, frames
+_HEADER = struct.Struct("<8sBB16sHIII")     # magic, codec, format, precision, bit depth, width, height, frames
 _RECORD = struct.Struct("<BBHIQQ")          # type, flags, reserved, payload length, digest S, digest X
 _COUNT_AT = _HEADER.size - 4
 # seeds of the frame digest, by DPB entry (an I frame: x_hat under seed 1)
@@ -46,16 +46,25 @@ class DigestMismatch(RuntimeError):
 
 
 # ---------------------------------------------------------------- the file
+def header_bit_depth(bit_depth):
+    """The header's bit-depth field for a source of ``bit_depth`` bits: 0
+    (8 bits / unspecified, what every 8-bit encode writes) or 9..16."""
+    if bit_depth not in (0,) + tuple(range(8, 17)):
+        raise ValueError(f"bit depth {bit_depth!r} is not 0 or 8..16")
+    return 0 if bit_depth == 8 else bit_depth
+
+
 class SequenceWriter:
-    def __init__(self, path, codec, fmt, precision, width, height):
+    def __init__(self, path, codec, fmt, precision, width, height, bit_depth=0):
         if codec not in CODECS or fmt not in FORMATS:
             raise ValueError(f"unknown codec / format {codec!r} / {fmt!r}")
+        field = header_bit_depth(bit_depth)
         name = precision.encode("ascii")
         if not 0 < len(name) <= 16:
             raise ValueError(f"precision name {precision!r} does not fit 16 bytes")
         self.frames = 0
         self.file = open(path, "wb")  # noqa: SIM115 (closed in close())
-        self.file.write(_HEADER.pack(MAGIC, CODECS.index(codec), FORMATS.index(fmt), name, 0, width, height,
+        self.file.write(_HEADER.pack(MAGIC, CODECS.index(codec), FORMATS.index(fmt), name, field, width, height,
                                      NOT_CLOSED))
 
     def write(self, frame_type, payload, twin=False, digest=None):
@@ -85,8 +94,9 @@ class SequenceWriter:
 
 
 class SequenceReader:
-    """Header fields as attributes (codec, format, precision, width, height,
-    frames); iterating yields {"type", "twin", "digest" (or None), "payload"}."""
+    """Header fields as attributes (codec, format, precision, bit_depth (the
+    source's, 8 for a field of 0), width, height, frames); iterating yields
+    {"type", "twin", "digest" (or None), "payload"}."""
 
     def __init__(self, path):
         self.path = path
@@ -95,10 +105,14 @@ class SequenceReader:
         if len(head) < _HEADER.size or head[:8] != MAGIC:
             self.close()
             raise SequenceFormatError(f"{path}: not a {MAGIC.decode()} sequence file")
-        _, codec, fmt, name, _, self.width, self.height, self.frames = _HEADER.unpack(head)
+        _, codec, fmt, name, depth, self.width, self.height, self.frames = _HEADER.unpack(head)
         if codec >= len(CODECS) or fmt >= len(FORMATS):
             self.close()
             raise SequenceFormatError(f"{path}: unknown codec / format code {codec} / {fmt}")
+        if depth != 0 and not 8 <= depth <= 16:
+            self.close()
+            raise SequenceFormatError(f"{path}: source bit depth {depth} is not 0 or 8..16")
+        self.bit_depth = depth or 8
         self.codec, self.format = CODECS[codec], FORMATS[fmt]
         self.precision = name.rstrip(b"\0").decode("ascii")
         if self.frames == NOT_CLOSED:
@@ -190,10 +204,12 @@ class SequenceEncoder:
     "type", "recon" (the (1, 3, H, W) reconstruction) and "digest".  The I/P
     schedule, the P codec's q and ``frame_idx`` are those of ``run_test`` /
     ``run_test_hem``: DC passes (q_in_ckpt, q_index) to both codecs and
-    ``frame_idx % 4``; HEM passes i_frame_q_scale and the two P scales."""
+    ``frame_idx % 4``; HEM passes i_frame_q_scale and the two P scales.
+    ``bit_depth`` is the source's, for the header only: no payload depends on it."""
 
     def __init__(self, i_net, p_net, path, width, height, gop_size, q_in_ckpt=False, q_index=None,
-                 i_frame_q_scale=None, p_frame_mv_y_q_scale=None, p_frame_y_q_scale=None, yuv420=False, digest=True):
+                 i_frame_q_scale=None, p_frame_mv_y_q_scale=None, p_frame_y_q_scale=None, yuv420=False, digest=True,
+                 bit_depth=8):
         self.codec, fmt, prec = _describe(i_net, p_net)
         if fmt != FORMATS[int(bool(yuv420))]:
             raise ValueError(f"the nets carry codec_format {fmt!r}, the caller asks for {FORMATS[int(bool(yuv420))]!r}")
@@ -206,7 +222,8 @@ class SequenceEncoder:
         self.q = (q_in_ckpt, q_index) if self.codec == "DC" else (i_frame_q_scale, p_frame_mv_y_q_scale,
                                                                   p_frame_y_q_scale)
         self.digest = FrameDigest(i_net.dev) if digest else None
-        self.writer = SequenceWriter(path, self.codec, fmt, prec, width, height)
+        header_bit_depth(bit_depth)     # before the file is created
+        self.writer = SequenceWriter(path, self.codec, fmt, prec, width, height, bit_depth=bit_depth)
         self.dpb = None
         self.n = 0
 
@@ -321,7 +338,11 @@ def main(argv=None):
     ap.add_argument("--p_frame_model_path", required=True)
     ap.add_argument("--yuv420", action="store_true", help="the checkpoints are YUV420 models (dist_in_yuv420)")
     ap.add_argument("--seq_path", required=True, help="the sequence file to write (encode) or read (decode)")
-    ap.add_argument("--src_type", choices=("png", "yuv420"), default=None)
+    ap.add_argument("--src_type", choices=("png", "yuv420", "rgb"), default=None,
+                    help="png folder, raw planar .yuv (4:2:0) or raw planar .rgb file")
+    ap.add_argument("--bit-depth", "--bit_depth", dest="bit_depth", type=int, default=None,
+                    help="encode: bits per sample of a raw .yuv / .rgb source (8; 9..16: little-endian uint16); "
+                         "decode: of the decoded-frame files (default: the source depth in the file's header)")
     ap.add_argument("--src_path")
     ap.add_argument("--src_width", type=int)
     ap.add_argument("--src_height", type=int)
@@ -339,6 +360,8 @@ def main(argv=None):
     args = {"seq_path": a.seq_path, "dist_in_yuv420": a.yuv420, "digest": not a.no_digest}
     if a.src_type is not None:
         args["src_type"] = a.src_type
+    if a.bit_depth is not None:
+        args["src_bit_depth" if a.mode == "encode" else "recon_bit_depth"] = a.bit_depth
     if a.mode == "encode":
         args.update(src_path=a.src_path, src_width=a.src_width, src_height=a.src_height, frame_num=a.frame_num,
                     gop_size=a.gop_size, q_in_ckpt=a.q_in_ckpt, i_frame_q_index=a.q_index,

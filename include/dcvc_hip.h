@@ -358,6 +358,66 @@ int dcvc_recon_to_u8_cross(dcvc_tensor x_hat, int h, int w, int to_rgb,
                            uint8_t *out, void *stream);
 
 /*
+ * High-bit-depth frames (frame16.hip; the fp32-source twins in crossfmt.hip):
+ * raw planar RGB and YUV420 sources of depth = 9..16 bits per sample, native
+ * (little-endian) uint16, as the reference's RGBReader / RGBWriter(bit_depth)
+ * read and write them (DCVC-DC/src/utils/video_reader.py:83-118,
+ * video_writer.py:50-80).  With max_val = (1 << depth) - 1:
+ *   in:  x = float32(sample) / float32(max_val), one IEEE division; samples
+ *        above max_val are not clamped;
+ *   out: uint16(clip(rint(float32(x) * float32(max_val)), 0, max_val)), rint
+ *        to even in fp32.
+ * Chroma resampling, BT.709, padding, the in-place clamp and the reduction
+ * order are those of the uint8 entry points above; depth 8 stays with them.
+ *
+ * These entry points take the 3-channel fp32 NHWC frame as scalars, not as a
+ * dcvc_tensor: base pointer of the (H, W, cstride) buffer, H, W, cstride and
+ * the channel offset coff of the frame's 3 channels (coff + 3 <= cstride).
+ * DCVC_HIP_EINVAL: a null pointer, a bad view, depth outside 9..16, a crop
+ * larger than the frame, odd sizes where 4:2:0 is involved.
+ *
+ * uint16 CHW RGB (3 x h x w) -> the padded frame; zero_pad = 0 replicates the
+ * last row / column (DCVC-DC), 1 pads with zeros (DCVC-HEM's harness).
+ */
+int dcvc_frame16_to_nhwc(const uint16_t *src, int h, int w, int depth,
+                         int zero_pad, float *out, int H, int W, int cstride,
+                         int coff, void *stream);
+/* dcvc_yuv420_to_nhwc on uint16 planes y (h x w) and uv (2 x h/2 x w/2). */
+int dcvc_yuv420p16_to_nhwc(const uint16_t *y, const uint16_t *uv, int h, int w,
+                           int depth, float *out, int H, int W, int cstride,
+                           int coff, void *stream);
+/* dcvc_frame_sse against a uint16 source (src = CHW RGB, or src = Y and
+ * uv = U|V planes for yuv420 = 1): same in-place clamp of x_hat, arithmetic,
+ * summation order and workspace (dcvc_frame_sse_workspace). */
+int dcvc_frame16_sse(float *x_hat, int H, int W, int cstride, int coff,
+                     const uint16_t *src, const uint16_t *uv, int h, int w,
+                     int depth, int yuv420, double *workspace, double *out3,
+                     void *stream);
+/* The top-left h x w crop of the decoded frame as uint16 samples (device):
+ *   yuv420 = 0: planar 3 x h x w, RGBWriter's out.rgb frame;
+ *   yuv420 = 1: Y plane then U, V planes of ycbcr444_to_420(clip(x_hat)). */
+int dcvc_recon_to_u16(const float *x_hat, int H, int W, int cstride, int coff,
+                      int h, int w, int depth, int yuv420, uint16_t *out,
+                      void *stream);
+/* The cross cases of dcvc_recon_to_u8_cross as uint16 samples:
+ *   to_rgb = 1: x_hat holds YCbCr 4:4:4 -> planar 3 x h x w RGB;
+ *   to_rgb = 0: x_hat holds RGB -> Y plane then U, V planes. */
+int dcvc_recon_to_u16_cross(const float *x_hat, int H, int W, int cstride,
+                            int coff, int h, int w, int depth, int to_rgb,
+                            uint16_t *out, void *stream);
+/* n uint16 samples -> fp32 sample / max_val (the reader's float planes, for
+ * the cross-format ingest and MS-SSIM). */
+int dcvc_u16_to_f32(const uint16_t *src, int64_t n, int depth, float *out,
+                    void *stream);
+/* dcvc_yuv420_to_rgb_nhwc and dcvc_rgb_to_yuv420_planes on fp32 source planes
+ * already in [0, 1] (dcvc_u16_to_f32's output). */
+int dcvc_yuv420f_to_rgb_nhwc(const float *y, const float *uv, int h, int w,
+                             float *out, int H, int W, int cstride, int coff,
+                             float *rgb_planes, void *stream);
+int dcvc_rgbf_to_yuv420_planes(const float *rgb, int h, int w, float *y_plane,
+                               float *uv_planes, void *stream);
+
+/*
  * Quadtree (four-part) prior step k, encoder side
  * (forward_four_part_prior write=True, DCVC-DC/src/models/common_model.py:
  * 142-252).  y: latent (C ch, fp32); params: common_params (3C ch:
