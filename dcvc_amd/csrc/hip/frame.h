@@ -1,7 +1,7 @@
-// Helpers shared by the harness-side frame kernels (frame.hip, crossfmt.hip):
-// the NHWC frame view, the uint8 -> [0, 1] conversion, scipy's order-0 zoom
-// index map, the fixed-order squared-error reduction and the uint8
-// quantisation of the decoded-frame writers.
+// Helpers shared by the harness-side frame kernels (frame.hip, crossfmt.hip,
+// frame16.hip, chroma.hip): the NHWC frame view, the uint8 / uint16 -> [0, 1]
+// conversions, scipy's order-0 zoom index map, the fixed-order squared-error
+// reduction and the uint8 / uint16 quantisation of the decoded-frame writers.
 #pragma once
 #include "common.h"
 
@@ -13,6 +13,9 @@ struct FView {
 };
 
 __device__ __forceinline__ float u8f(uint8_t v) { return (float)v / 255.f; }
+
+// a 9..16-bit sample with mx = float32((1 << depth) - 1): one IEEE division
+__device__ __forceinline__ float u16f(uint16_t v, float mx) { return (float)v / mx; }
 
 // scipy.ndimage.zoom(uv, (1, 2, 2), order=0) as ycbcr420_to_444(order=0)
 // calls it (DCVC-DC/src/transforms/functional.py:61-72): output index i of an
@@ -59,6 +62,10 @@ __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 
 
 __device__ __forceinline__ uint8_t q255(float v) {
   return (uint8_t)fminf(fmaxf(rintf(v * 255.f), 0.f), 255.f);  // np.clip(np.rint(v * 255), 0, 255)
+}
+
+__device__ __forceinline__ uint16_t q16(float v, float mx) {
+  return (uint16_t)fminf(fmaxf(rintf(v * mx), 0.f), mx);  // np.clip(np.rint(v * max_val), 0, max_val)
 }
 
 // Fixed-order final reduction of the per-block partials: out[c] = sum_b part[3b + c].

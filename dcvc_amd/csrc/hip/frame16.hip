@@ -20,12 +20,6 @@
 
 namespace {
 
-__device__ __forceinline__ float u16f(uint16_t v, float mx) { return (float)v / mx; }
-
-__device__ __forceinline__ uint16_t q16(float v, float mx) {
-  return (uint16_t)fminf(fmaxf(rintf(v * mx), 0.f), mx);  // np.clip(np.rint(v * max_val), 0, max_val)
-}
-
 // frame_kernel (misc.hip) on uint16 CHW samples: one thread per output element
 __global__ void frame16_kernel(const uint16_t *__restrict__ src, int h, int w, float mx, int zero_pad, FView y) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

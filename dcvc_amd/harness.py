@@ -34,6 +34,12 @@ as they are; a sample is x / ((1 << d) - 1).  A source of the codec's format is
 read by the 16-bit kernels directly (frame16.hip), the cross-format ingest and
 MS-SSIM go through fp32 planes, and ``ReconWriter`` stores uint16 out.yuv /
 out.rgb.  8 bits is the uint8 code, unchanged.
+
+Chroma layouts: planar YUV 4:2:2 and 4:4:4 files (``src_type`` "yuv422" /
+"yuv444", 8..16 bits) go through chroma.hip.  The YUV codecs code a 4:4:4
+tensor, so a 4:4:4 source is taken as it is and a 4:2:2 source is resampled
+along x only; distortion and out.yuv are at the source's own chroma
+resolution.  4:2:0 stays on the kernels above.
 """
 import contextlib
 import os
@@ -66,19 +72,30 @@ class YUVReader:
     its ycbcr420_to_rgb happen on the GPU (FrameStage).  ``bit_depth`` 9..16
     (beyond the reference, whose YUVReader is 8-bit): little-endian uint16
     samples, full range like the 8-bit rule, returned as uint16 planes; frame
-    and skip sizes double."""
+    and skip sizes double.  ``src_format`` "422" | "444" (beyond the reference,
+    which stops at "420"): the same planar layout with chroma planes of
+    h x w/2 or h x w samples; ``uv`` is then (2, h, w/2) or (2, h, w).  The
+    layout belongs to the file, so it is this constructor's argument and never
+    a ``dst_format``."""
 
     def __init__(self, src_path, width, height, src_format="420", skip_frame=0, bit_depth=8):
-        if src_format != "420":
-            raise ValueError("only 420 sources are supported (video_reader.py:127)")
-        if _check_bit_depth(bit_depth) > 8 and (width % 2 or height % 2):
+        if src_format not in K.CHROMA_FORMATS:
+            raise ValueError(f"unknown src_format {src_format!r}: a YUV file is '420', '422' or '444'")
+        self.src_format = src_format
+        self.sub_x, self.sub_y = K.CHROMA_FORMATS[src_format]
+        if src_format == "420" and _check_bit_depth(bit_depth) > 8 and (width % 2 or height % 2):
             raise ValueError(f"a 4:2:0 file needs even sizes, not {width} x {height}")
+        if src_format == "422" and width % 2:
+            raise ValueError(f"a 4:2:2 file needs an even width, not {width} x {height}")
         if not src_path.endswith(".yuv"):
             src_path = src_path + ".yuv"
         self.src_path, self.width, self.height = src_path, width, height
         self.bit_depth, self.dtype = bit_depth, _sample_dtype(bit_depth)
         self.y_size = width * height * self.dtype.itemsize
-        self.uv_size = width * height // 2 * self.dtype.itemsize
+        if src_format == "420":
+            self.uv_size = width * height // 2 * self.dtype.itemsize
+        else:
+            self.uv_size = 2 * (height // self.sub_y) * (width // self.sub_x) * self.dtype.itemsize
         self.eof = False
         self.file = open(src_path, "rb")  # noqa: SIM115 (closed in close())
         for _ in range(skip_frame):
@@ -102,7 +119,7 @@ class YUVReader:
         if r is None:
             return None, None
         y = np.frombuffer(r[0], dtype=self.dtype).reshape(self.height, self.width)
-        uv = np.frombuffer(r[1], dtype=self.dtype).reshape(2, self.height // 2, self.width // 2)
+        uv = np.frombuffer(r[1], dtype=self.dtype).reshape(2, self.height // self.sub_y, self.width // self.sub_x)
         return y, uv
 
     def close(self):
@@ -215,24 +232,36 @@ class FrameStage:
     uploaded as they are.  A source of the codec's format is read directly by
     the 16-bit kernels (frame16.hip); one of the other format is first turned
     into fp32 planes (``dcvc_u16_to_f32``) and then converted as above.  8 is
-    the uint8 code, untouched."""
+    the uint8 code, untouched.
+
+    ``src_format`` "422" | "444": (y, uv) planes of a planar YUV source in that
+    chroma layout, at any depth (chroma.hip).  For a YUV codec the planes are
+    taken as they are (4:2:2: zoomed along x) and the distortion is measured at
+    the source's chroma resolution; for an RGB codec they are converted
+    (``src_f32``: the planar fp32 RGB source) as a 4:2:0 source is."""
 
     def __init__(self, h, w, align, yuv420, zero_pad, frame_num, device, src_format=None, bit_depth=8):
         self.h, self.w, self.yuv, self.zero_pad = h, w, yuv420, zero_pad
         codec_format = "420" if yuv420 else "rgb"
         src_format = codec_format if src_format is None else src_format
-        if src_format not in ("rgb", "420"):
+        if src_format not in ("rgb", "420", "422", "444"):
             raise ValueError(f"unknown src_format {src_format!r}")
         self.bit_depth = _check_bit_depth(bit_depth)
         self.deep = bit_depth > 8
-        self.src_yuv = src_format == "420"
-        if self.deep and (self.src_yuv or yuv420) and (h % 2 or w % 2):
+        self.src_yuv = src_format != "rgb"
+        # a 4:2:2 / 4:4:4 source (chroma.hip): its layout; None for the older paths
+        self.chroma = src_format if src_format in ("422", "444") else None
+        if self.chroma is None and self.deep and (self.src_yuv or yuv420) and (h % 2 or w % 2):
             raise ValueError(f"4:2:0 needs even sizes, not {w} x {h}")
-        self.cross = src_format != codec_format
+        if self.chroma == "422" and w % 2:
+            raise ValueError(f"4:2:2 needs an even width, not {w} x {h}")
+        if self.chroma is not None and zero_pad:
+            raise ValueError("a 4:2:2 / 4:4:4 source is padded by replication")
+        self.cross = self.src_yuv != bool(yuv420)
         self.src_f32 = None
         self.raw_f32 = None       # bit_depth > 8: the uint16 source as fp32 planes (cross ingest, MS-SSIM)
         if self.cross:
-            if zero_pad or h % 2 or w % 2:
+            if zero_pad or (self.chroma is None and (h % 2 or w % 2)):
                 raise ValueError("a converted source needs even sizes and replicate padding")
             if yuv420:
                 self.src_f32 = (torch.empty((h, w), dtype=torch.float32, device=device),
@@ -279,12 +308,21 @@ class FrameStage:
         of the same frame."""
         if self.cross:
             return self.src_f32
+        if self.chroma is not None:
+            raise ValueError("MS-SSIM of a 4:2:2 / 4:4:4 source on a YUV codec is not supported")
         return self._raw_f32(dframe) if self.deep else None
 
     def load(self, dframe):
         """Device source frame -> padded NHWC fp32 codec input (test_video.py:
         108-132: ycbcr420_to_444(order=0) for YUV, x / 255, F.pad; for a source
         of the other format, the reader's conversion first)."""
+        if self.chroma is not None:     # 4:2:2 / 4:4:4 planes, any depth (chroma.hip)
+            if self.cross:
+                K.yuvp_to_rgb_nhwc(dframe[0], dframe[1], self.h, self.w, self.bit_depth, self.chroma, self.x,
+                                   self.src_f32[0])
+            else:
+                K.yuvp_to_nhwc(dframe[0], dframe[1], self.h, self.w, self.bit_depth, self.chroma, self.x)
+            return self.x
         if self.deep:
             return self._load16(dframe)
         if self.cross and self.yuv:
@@ -321,6 +359,8 @@ class FrameStage:
             K.frame_sse_f32(r, self.src_f32[0], self.h, self.w, self.ws, self.sse[slot], uv_f32=self.src_f32[1])
         elif self.cross:
             K.frame_sse_f32(r, self.src_f32[0], self.h, self.w, self.ws, self.sse[slot])
+        elif self.chroma is not None:
+            K.yuvp_sse(r, dframe[0], dframe[1], self.h, self.w, self.bit_depth, self.chroma, self.ws, self.sse[slot])
         elif self.deep and self.yuv:
             K.frame16_sse(r, dframe[0], self.h, self.w, self.bit_depth, self.ws, self.sse[slot], uv_u16=dframe[1])
         elif self.deep:
@@ -479,24 +519,37 @@ class ReconWriter:
     stays 8-bit.
     The reference's cross cases (a 4:2:0 frame into PNGWriter, an RGB frame into
     YUVWriter, functional.py:16-58) are converted and quantised on the GPU as
-    well (dcvc_recon_to_u8_cross) and take the same pinned-copy path."""
+    well (dcvc_recon_to_u8_cross) and take the same pinned-copy path.
+    ``chroma`` "422" | "444" (kind "yuv" only): out.yuv in that planar layout,
+    from either codec format and at any depth (dcvc_recon_to_yuvp)."""
 
-    def __init__(self, path, h, w, kind, src_format, device, bit_depth=8):
+    def __init__(self, path, h, w, kind, src_format, device, bit_depth=8, chroma="420"):
         from concurrent.futures import ThreadPoolExecutor
         if kind not in ("png", "yuv", "hem_png", "rgb"):
             raise ValueError(f"unknown writer kind {kind!r}")
+        if chroma not in K.CHROMA_FORMATS:
+            raise ValueError(f"unknown chroma format {chroma!r}")
+        if chroma != "420" and kind != "yuv":
+            raise ValueError(f"chroma {chroma!r} is the layout of an out.yuv file, not of {kind!r} output")
         self.bit_depth = _check_bit_depth(bit_depth)
         self.deep = bit_depth > 8
+        # out.yuv at 4:2:2 / 4:4:4 (dcvc_recon_to_yuvp, either codec format); None: the older paths
+        self.chroma = chroma if chroma != "420" else None
         if self.deep and kind in ("png", "hem_png"):
             raise ValueError(f"PNG output is 8-bit; write {bit_depth}-bit frames as 'rgb' or 'yuv'")
-        if self.deep and (kind == "yuv" or src_format == "420") and (h % 2 or w % 2):
+        if self.chroma is None and self.deep and (kind == "yuv" or src_format == "420") and (h % 2 or w % 2):
             raise ValueError(f"4:2:0 needs even sizes, not {w} x {h}")
+        if self.chroma == "422" and w % 2:
+            raise ValueError(f"4:2:2 needs an even width, not {w} x {h}")
         os.makedirs(path, exist_ok=True)
         self.path, self.h, self.w, self.kind, self.fmt = path, h, w, kind, src_format
         self.yuv_out = kind == "yuv"
         self.quant_yuv = src_format == "420"
         self.cross = self.quant_yuv != self.yuv_out
-        self.n = h * w + 2 * (h // 2) * (w // 2) if self.yuv_out else 3 * h * w
+        if self.chroma is not None:
+            self.n = sum(K.yuvp_sizes(h, w, chroma)[2:])
+        else:
+            self.n = h * w + 2 * (h // 2) * (w // 2) if self.yuv_out else 3 * h * w
         self.dtype = torch.int16 if self.deep else torch.uint8      # uint16 bits travel as int16
         self.dev_buf = torch.empty(self.n, dtype=self.dtype, device=device)
         self.pool = ThreadPoolExecutor(1)
@@ -509,7 +562,9 @@ class ReconWriter:
     def write(self, recon, frame_idx):
         from .dc.video_model import as_act
         x = as_act(recon)
-        if self.deep and self.cross:
+        if self.chroma is not None:
+            K.recon_to_yuvp(x, self.h, self.w, self.bit_depth, self.chroma, not self.quant_yuv, self.dev_buf)
+        elif self.deep and self.cross:
             K.recon_to_u16_cross(x, self.h, self.w, self.bit_depth, not self.yuv_out, self.dev_buf)
         elif self.deep:
             K.recon_to_u16(x, self.h, self.w, self.bit_depth, self.quant_yuv, self.dev_buf)
@@ -577,11 +632,13 @@ def calc_psnr_from_sse(sse, n, data_range=1.0):
     return 999.9
 
 
-def psnr_yuv(sse3, h, w):
-    """(psnr_y, psnr_u, psnr_v, (6 y + u + v) / 8), test_video.py:177-181."""
+def psnr_yuv(sse3, h, w, chroma="420"):
+    """(psnr_y, psnr_u, psnr_v, (6 y + u + v) / 8), test_video.py:177-181;
+    the chroma planes have the size of the source's ``chroma`` format."""
+    sx, sy = K.chroma_sub(chroma)
     py = calc_psnr_from_sse(sse3[0], h * w)
-    pu = calc_psnr_from_sse(sse3[1], (h // 2) * (w // 2))
-    pv = calc_psnr_from_sse(sse3[2], (h // 2) * (w // 2))
+    pu = calc_psnr_from_sse(sse3[1], (h // sy) * (w // sx))
+    pv = calc_psnr_from_sse(sse3[2], (h // sy) * (w // sx))
     return py, pu, pv, (6 * py + pu + pv) / 8
 
 
@@ -650,12 +707,16 @@ def generate_log_json(frame_num, frame_pixel_num, test_time, frame_types, bits, 
     return log
 
 
+YUV_SRC_TYPES = {"yuv420": "420", "yuv422": "422", "yuv444": "444"}   # src_type -> YUVReader's src_format
+
+
 def _reader(args, yuv):
     if "src_reader" in args:
         return args["src_reader"]
     depth = args.get("src_bit_depth", 8)
-    if args["src_type"] == "yuv420":
-        return YUVReader(args["src_path"], args["src_width"], args["src_height"], bit_depth=depth)
+    if args["src_type"] in YUV_SRC_TYPES:
+        return YUVReader(args["src_path"], args["src_width"], args["src_height"],
+                         src_format=YUV_SRC_TYPES[args["src_type"]], bit_depth=depth)
     if args["src_type"] == "rgb":
         return RGBReader(args["src_path"], args["src_width"], args["src_height"], bit_depth=depth)
     if args["src_type"] == "png":
@@ -666,11 +727,23 @@ def _reader(args, yuv):
 
 
 def _src_format(src_type, codec_fmt):
-    """"rgb" | "420": what a source of ``src_type`` ('png' | 'rgb' | 'yuv420',
-    None: the codec's own format) hands over."""
-    if src_type not in (None, "yuv420", "png", "rgb"):
+    """"rgb" | "420" | "422" | "444": what a source of ``src_type`` ('png' |
+    'rgb' | 'yuv420' | 'yuv422' | 'yuv444', None: the codec's own format)
+    hands over."""
+    if src_type not in (None, "png", "rgb", *YUV_SRC_TYPES):
         raise ValueError(f"unknown src_type {src_type!r}")
-    return codec_fmt if src_type is None else ("420" if src_type == "yuv420" else "rgb")
+    return codec_fmt if src_type is None else YUV_SRC_TYPES.get(src_type, "rgb")
+
+
+def _dst_format(src_fmt):
+    """What the drivers ask a reader for: "rgb", or "420" for every YUV source
+    (the chroma layout is the reader's own, never a ``dst_format``)."""
+    return "rgb" if src_fmt == "rgb" else "420"
+
+
+def _chroma(src_fmt):
+    """The chroma layout of the decoded-frame file that goes with a source."""
+    return src_fmt if src_fmt in ("422", "444") else "420"
 
 
 def _bit_depths(args, default=8):
@@ -693,7 +766,7 @@ def _writer_kind(src_type, src_fmt, bit_depth):
 def run_test(p_frame_net, i_frame_net, args):
     """DCVC-DC/test_video.py:71-237 on the GPU codecs.  ``args`` takes the
     reference's keys (frame_num, gop_size, write_stream, bin_folder,
-    src_type 'png' | 'yuv420' | 'rgb' (a raw planar .rgb file), src_bit_depth
+    src_type 'png' | 'yuv420' | 'yuv422' | 'yuv444' | 'rgb' (a raw planar .rgb file), src_bit_depth
     (8; 9..16 for uint16 .rgb / .yuv files), recon_bit_depth (the decoded-frame
     files' depth, the source's by default), src_path, src_width, src_height,
     dist_in_yuv420, q_in_ckpt, i_frame_q_index, verbose, calc_ssim) plus an
@@ -710,6 +783,9 @@ def run_test(p_frame_net, i_frame_net, args):
     src_type = args.get("src_type")
     src_fmt = _src_format(src_type, codec_fmt)
     src_depth, recon_depth = _bit_depths(args)
+    if args.get("calc_ssim") and yuv and _chroma(src_fmt) != "420":
+        raise ValueError(f"calc_ssim on a YUV codec needs a 4:2:0 or RGB source, not {src_type!r}: "
+                         "per-plane MS-SSIM at other chroma plane sizes is not supported")
     device = i_frame_net.dev
     reader = _reader(args, yuv)
     h, w = args["src_height"], args["src_width"]
@@ -718,7 +794,7 @@ def run_test(p_frame_net, i_frame_net, args):
     writer = None
     if args.get("save_decoded_frame"):   # test_video.py:84-88
         writer = ReconWriter(args["recon_path"], h, w, _writer_kind(src_type, src_fmt, recon_depth), codec_fmt,
-                             device, bit_depth=recon_depth)
+                             device, bit_depth=recon_depth, chroma=_chroma(src_fmt))
     ms = None
     if args.get("calc_ssim"):
         ms = MsSsim(h, w, frame_num, device) if yuv else MsSsimRGB(h, w, frame_num, device)
@@ -729,8 +805,8 @@ def run_test(p_frame_net, i_frame_net, args):
     dpb = None
     with torch.no_grad(), (writer if writer is not None else contextlib.nullcontext()):
         for frame_idx in range(frame_num):
-            frame = reader.read_one_frame(dst_format=src_fmt)
-            if frame is None or (src_fmt == "420" and frame[0] is None):
+            frame = reader.read_one_frame(dst_format=_dst_format(src_fmt))
+            if frame is None or (src_fmt != "rgb" and frame[0] is None):
                 raise ValueError(f"source ended at frame {frame_idx} of {frame_num}")
             dframe = stage.upload(frame)
             x = stage.load(dframe)
@@ -775,7 +851,7 @@ def run_test(p_frame_net, i_frame_net, args):
               f"average decoding time {dec_t / p_frame_number * 1000:.0f} ms.")
     zeros = [0.0] * frame_num
     if yuv:
-        per = [psnr_yuv(sse[i], h, w) for i in range(frame_num)]
+        per = [psnr_yuv(sse[i], h, w, _chroma(src_fmt)) for i in range(frame_num)]
         mv = ms.values(frame_num) if ms is not None else [(0.0, 0.0, 0.0, 0.0)] * frame_num
         log = generate_log_json(frame_num, h * w, test_time, frame_types, bits, [p[3] for p in per],
                                 [m[3] for m in mv], [p[0] for p in per], [p[1] for p in per], [p[2] for p in per],
@@ -916,8 +992,8 @@ def encode_video(i_frame_net, p_frame_net, args):
     with SequenceEncoder(i_frame_net, p_frame_net, args["seq_path"], w, h, gop_size, yuv420=yuv,
                          digest=bool(args.get("digest", True)), bit_depth=src_depth, **q) as enc:
         for frame_idx in range(frame_num):
-            frame = reader.read_one_frame(dst_format=src_fmt)
-            if frame is None or (src_fmt == "420" and frame[0] is None):
+            frame = reader.read_one_frame(dst_format=_dst_format(src_fmt))
+            if frame is None or (src_fmt != "rgb" and frame[0] is None):
                 raise ValueError(f"source ended at frame {frame_idx} of {frame_num}")
             dframe = stage.upload(frame)
             out = enc.encode(stage.load(dframe))
@@ -934,7 +1010,7 @@ def encode_video(i_frame_net, p_frame_net, args):
         log = generate_log_json_hem(frame_num, frame_types, bits, [psnr_rgb(sse[i], h, w) for i in range(frame_num)],
                                     zeros, h * w, test_time)
     elif yuv:
-        per = [psnr_yuv(sse[i], h, w) for i in range(frame_num)]
+        per = [psnr_yuv(sse[i], h, w, _chroma(src_fmt)) for i in range(frame_num)]
         log = generate_log_json(frame_num, h * w, test_time, frame_types, bits, [p[3] for p in per], zeros,
                                 [p[0] for p in per], [p[1] for p in per], [p[2] for p in per], zeros, zeros, zeros,
                                 verbose=verbose >= 1)
@@ -973,7 +1049,7 @@ def decode_video(i_frame_net, p_frame_net, args):
                                      bit_depth=depth)
             else:
                 writer = ReconWriter(args["recon_path"], h, w, _writer_kind(src_type, src_fmt, depth), codec_fmt,
-                                     i_frame_net.dev, bit_depth=depth)
+                                     i_frame_net.dev, bit_depth=depth, chroma=_chroma(src_fmt))
         with (writer if writer is not None else contextlib.nullcontext()):
             for frame_idx, out in enumerate(dec):
                 frame_types.append(0 if out["type"] == "I" else 1)

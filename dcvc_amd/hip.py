@@ -114,6 +114,10 @@ HIP_SYMBOLS = [
     ("dcvc_u16_to_f32", _i, [_vp, ctypes.c_int64, _i, _vp, _vp]),
     ("dcvc_yuv420f_to_rgb_nhwc", _i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     ("dcvc_rgbf_to_yuv420_planes", _i, [_vp, _i, _i, _vp, _vp, _vp]),
+    ("dcvc_yuvp_to_nhwc", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    ("dcvc_yuvp_to_rgb_nhwc", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    ("dcvc_yuvp_sse", _i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    ("dcvc_recon_to_yuvp", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     ("dcvc_quadtree_encode_step", _i, [_T, _T, _T, _i, _T, _T, _vp, _vp, _f, _f, _vp]),
     ("dcvc_quadtree_indexes_step", _i, [_T, _T, _i, _vp, _f, _f, _vp]),
     ("dcvc_quadtree_decode_step", _i, [_T, _T, _i, _vp, _T, _T, _vp]),
@@ -956,6 +960,86 @@ def rgbf_to_yuv420_planes(src_f32, h, w, y_f32, uv_f32):
     assert y_f32.is_contiguous() and uv_f32.is_contiguous()
     check(lib().dcvc_rgbf_to_yuv420_planes(src_f32.data_ptr(), h, w, y_f32.data_ptr(), uv_f32.data_ptr(), stream()),
           "rgbf_to_yuv420_planes")
+
+
+# ---- planar YUV at any chroma layout, 8..16 bits (chroma.hip).  The harness
+# routes 4:4:4 and 4:2:2 here; "420" is the tests' tie to the 4:2:0 kernels.
+CHROMA_SYMBOLS = ("dcvc_yuvp_to_nhwc", "dcvc_yuvp_to_rgb_nhwc", "dcvc_yuvp_sse", "dcvc_recon_to_yuvp")
+CHROMA_FORMATS = {"444": (1, 1), "422": (2, 1), "420": (2, 2)}
+
+
+def chroma_sub(chroma):
+    """(sub_x, sub_y) of a chroma format: "444" | "422" | "420", or the pair itself."""
+    if isinstance(chroma, str) and chroma in CHROMA_FORMATS:
+        return CHROMA_FORMATS[chroma]
+    if isinstance(chroma, tuple) and chroma in CHROMA_FORMATS.values():
+        return chroma
+    raise ValueError(f"unknown chroma format {chroma!r}")
+
+
+def check_depth8(bit_depth):
+    """A chroma-layout path's depth: 8..16."""
+    if not isinstance(bit_depth, int) or isinstance(bit_depth, bool) or not 8 <= bit_depth <= 16:
+        raise ValueError(f"bit depth {bit_depth!r} is outside 8..16")
+    return bit_depth
+
+
+def yuvp_sizes(h, w, chroma):
+    """(sub_x, sub_y, luma samples, samples of U and V together) of an h x w frame."""
+    sx, sy = chroma_sub(chroma)
+    if h < 1 or w < 1 or h % sy or w % sx:
+        raise ValueError(f"a {w} x {h} frame does not divide into {sx} x {sy} chroma footprints")
+    return sx, sy, h * w, 2 * (h // sy) * (w // sx)
+
+
+def _smp(t, n, depth):
+    """Device samples of ``depth`` bits: uint8 at 8, a 2-byte integer type above."""
+    if depth == 8:
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.numel() == n, (t.dtype, t.numel(), n)
+        return t.data_ptr()
+    return _s16(t, n)
+
+
+def yuvp_to_nhwc(y_s, uv_s, h, w, depth, chroma, out):
+    """Device planes Y (h x w) and U|V (2 x h/sy x w/sx) of a planar YUV source
+    -> padded NHWC YCbCr 4:4:4 fp32 (dcvc_yuvp_to_nhwc)."""
+    sx, sy, ny, nuv = yuvp_sizes(h, w, chroma)
+    check_depth8(depth)
+    check(lib().dcvc_yuvp_to_nhwc(_smp(y_s, ny, depth), _smp(uv_s, nuv, depth), h, w, depth, sx, sy, *_fv(out),
+                                  stream()), "yuvp_to_nhwc")
+    return out
+
+
+def yuvp_to_rgb_nhwc(y_s, uv_s, h, w, depth, chroma, out, rgb_planes):
+    """The same planes -> padded NHWC RGB fp32 and the planar 3 x h x w fp32
+    RGB source (dcvc_yuvp_to_rgb_nhwc)."""
+    sx, sy, ny, nuv = yuvp_sizes(h, w, chroma)
+    check_depth8(depth)
+    assert rgb_planes.dtype == torch.float32 and rgb_planes.numel() == 3 * h * w and rgb_planes.is_contiguous()
+    check(lib().dcvc_yuvp_to_rgb_nhwc(_smp(y_s, ny, depth), _smp(uv_s, nuv, depth), h, w, depth, sx, sy, *_fv(out),
+                                      rgb_planes.data_ptr(), stream()), "yuvp_to_rgb_nhwc")
+    return out
+
+
+def yuvp_sse(x_hat, y_s, uv_s, h, w, depth, chroma, workspace, out3):
+    """frame_sse of a YCbCr 4:4:4 frame against a planar YUV source of any
+    chroma layout (dcvc_yuvp_sse)."""
+    sx, sy, ny, nuv = yuvp_sizes(h, w, chroma)
+    check_depth8(depth)
+    assert out3.dtype == torch.float64 and out3.numel() >= 3
+    check(lib().dcvc_yuvp_sse(*_fv(x_hat), _smp(y_s, ny, depth), _smp(uv_s, nuv, depth), h, w, depth, sx, sy,
+                              workspace.data_ptr(), out3.data_ptr(), stream()), "yuvp_sse")
+    return out3
+
+
+def recon_to_yuvp(x_hat, h, w, depth, chroma, from_rgb, out):
+    """Decoded frame (YCbCr 4:4:4, or RGB with ``from_rgb``) -> the Y | U | V
+    samples of a planar file of that layout and depth (dcvc_recon_to_yuvp)."""
+    sx, sy, ny, nuv = yuvp_sizes(h, w, chroma)
+    check_depth8(depth)
+    check(lib().dcvc_recon_to_yuvp(*_fv(x_hat), h, w, depth, sx, sy, 1 if from_rgb else 0,
+                                   _smp(out, ny + nuv, depth), stream()), "recon_to_yuvp")
+    return out
 
 
 def yuv_planes_f64(x_hat, y_u8, uv_u8, h, w, src, rec):

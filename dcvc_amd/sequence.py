@@ -338,8 +338,9 @@ def main(argv=None):
     ap.add_argument("--p_frame_model_path", required=True)
     ap.add_argument("--yuv420", action="store_true", help="the checkpoints are YUV420 models (dist_in_yuv420)")
     ap.add_argument("--seq_path", required=True, help="the sequence file to write (encode) or read (decode)")
-    ap.add_argument("--src_type", choices=("png", "yuv420", "rgb"), default=None,
-                    help="png folder, raw planar .yuv (4:2:0) or raw planar .rgb file")
+    ap.add_argument("--src_type", choices=("png", "yuv420", "yuv422", "yuv444", "rgb"), default=None,
+                    help="png folder, raw planar .yuv (4:2:0, 4:2:2 or 4:4:4) or raw planar .rgb file; "
+                         "decode: the layout of the decoded-frame files")
     ap.add_argument("--bit-depth", "--bit_depth", dest="bit_depth", type=int, default=None,
                     help="encode: bits per sample of a raw .yuv / .rgb source (8; 9..16: little-endian uint16); "
                          "decode: of the decoded-frame files (default: the source depth in the file's header)")

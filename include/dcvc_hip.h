@@ -418,6 +418,47 @@ int dcvc_rgbf_to_yuv420_planes(const float *rgb, int h, int w, float *y_plane,
                                float *uv_planes, void *stream);
 
 /*
+ * Planar YUV frames at any chroma layout (chroma.hip).  A layout is (sub_x,
+ * sub_y): 4:4:4 = (1, 1), 4:2:2 = (2, 1), 4:2:0 = (2, 2); a frame is Y (h x w),
+ * then U and V (h / sub_y x w / sub_x each).  depth = 8..16: the sample
+ * pointers are uint8 at 8 and native (little-endian) uint16 above, with the
+ * sample rule of the high-bit-depth entry points (max_val = 255 at 8, where it
+ * is the uint8 rule).  The frame view is passed as scalars as above.
+ *   4:4:4: the chroma planes as they are;
+ *   4:2:2: the horizontal half of the 4:2:0 arithmetic (order-0 / order-1
+ *          zoom along x in, mean of each horizontal pair out);
+ *   4:2:0: bit-equal to the uint8 / uint16 4:2:0 entry points above (the
+ *          harness keeps routing 4:2:0 to those).
+ * DCVC_HIP_EINVAL: a null pointer, a bad view, depth outside 8..16, an unknown
+ * (sub_x, sub_y), odd w with sub_x = 2, odd h with sub_y = 2, a view smaller
+ * than the frame.
+ *
+ * Source into a YUV codec: y, uv -> the padded YCbCr 4:4:4 frame. */
+int dcvc_yuvp_to_nhwc(const void *y, const void *uv, int h, int w, int depth,
+                      int sub_x, int sub_y, float *out, int H, int W,
+                      int cstride, int coff, void *stream);
+/* Source into an RGB codec: ycbcr_to_rgb of the order-1 upsampled planes into
+ * the padded frame, and the h x w crop as planar fp32 RGB (3 x h x w). */
+int dcvc_yuvp_to_rgb_nhwc(const void *y, const void *uv, int h, int w,
+                          int depth, int sub_x, int sub_y, float *out, int H,
+                          int W, int cstride, int coff, float *rgb_planes,
+                          void *stream);
+/* dcvc_frame_sse against such a source: x_hat (YCbCr 4:4:4) clamped in place
+ * over the whole view; out3 = the squared-error sums of Y (h x w) and of U, V
+ * at the source's chroma resolution (clipped footprint means of the clamped
+ * values).  Workspace: dcvc_frame_sse_workspace. */
+int dcvc_yuvp_sse(float *x_hat, int H, int W, int cstride, int coff,
+                  const void *y, const void *uv, int h, int w, int depth,
+                  int sub_x, int sub_y, double *workspace, double *out3,
+                  void *stream);
+/* The top-left h x w crop of the decoded frame as the samples of a planar
+ * file: Y | U | V.  from_rgb = 0: x_hat holds YCbCr 4:4:4; from_rgb = 1: x_hat
+ * holds RGB (rgb_to_ycbcr per pixel, chroma averaged unclipped, then clipped). */
+int dcvc_recon_to_yuvp(const float *x_hat, int H, int W, int cstride, int coff,
+                       int h, int w, int depth, int sub_x, int sub_y,
+                       int from_rgb, void *out, void *stream);
+
+/*
  * Quadtree (four-part) prior step k, encoder side
  * (forward_four_part_prior write=True, DCVC-DC/src/models/common_model.py:
  * 142-252).  y: latent (C ch, fp32); params: common_params (3C ch:
