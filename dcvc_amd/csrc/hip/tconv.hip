@@ -189,7 +189,10 @@ extern "C" int dcvc_internal_tconv(const dcvc_conv_args *a, void *stream) {
   if (!g_enable) return DCVC_HIP_EUNSUPPORTED;
   if (a->kh != a->kw || a->pad != a->kh / 2 || a->shuffle) return DCVC_HIP_EUNSUPPORTED;
   if (a->x.dtype != DCVC_F32 || a->y.dtype != DCVC_F32) return DCVC_HIP_EUNSUPPORTED;
-  if (a->in_op != DCVC_IN_NONE && !(a->in_op == DCVC_IN_LRELU)) return DCVC_HIP_EUNSUPPORTED;
+  // the kernel computes the input leaky ReLU as max(v, in_slope * v): the
+  // select v >= 0 ? v : in_slope * v for every in_slope <= 1, negative ones
+  // included, and for no other (nor for NaN, which the comparison refuses too)
+  if (a->in_op != DCVC_IN_NONE && !(a->in_op == DCVC_IN_LRELU && a->in_slope <= 1.f)) return DCVC_HIP_EUNSUPPORTED;
   if (a->res2.ptr && !a->res.ptr) return DCVC_HIP_EUNSUPPORTED;
   if ((a->res.ptr && a->res.dtype != DCVC_F32) || (a->res2.ptr && a->res2.dtype != DCVC_F32)) return DCVC_HIP_EUNSUPPORTED;
   const bool ci = a->cin == 2 && (a->kh == 3 || a->kh == 1) && a->cout % 64 == 0 && a->cout <= 256 &&
@@ -209,7 +212,9 @@ extern "C" int dcvc_internal_tconv(const dcvc_conv_args *a, void *stream) {
   p.cout = a->cout;
   p.kt = a->kh * a->kw;
   p.in_lrelu = a->in_op == DCVC_IN_LRELU;
-  p.vec_out = f32_pieces_ok(a->y, 4);   // (no rule for the input and residual views or the slopes)
+  // (no rule for the input and residual views; the output slope is apply_act's
+  // select, exact for any value; the input slope's rule is above)
+  p.vec_out = f32_pieces_ok(a->y, 4);
   p.nq = (p.Wo + 3) / 4;
   if (!p.bias) return DCVC_HIP_EUNSUPPORTED;
   // 32-bit buffer offsets of the input map
