@@ -64,6 +64,26 @@ def _sample_dtype(bit_depth):
     return np.dtype(np.uint8) if _check_bit_depth(bit_depth) == 8 else np.dtype("<u2")
 
 
+def _frame_index(index):
+    if not isinstance(index, (int, np.integer)) or isinstance(index, bool) or index < 0:
+        raise ValueError(f"frame index {index!r} is not a non-negative int")
+    return int(index)
+
+
+def _pread(file, n, offset):
+    """Up to ``n`` bytes of ``file`` at ``offset``, without moving its cursor
+    (and so safe beside sequential reads of the same object)."""
+    chunks = []
+    while n > 0:
+        b = os.pread(file.fileno(), n, offset)
+        if not b:
+            break
+        chunks.append(b)
+        n -= len(b)
+        offset += len(b)
+    return chunks[0] if len(chunks) == 1 else b"".join(chunks)
+
+
 class YUVReader:
     """Raw YUV420 file reader (DCVC-DC/src/utils/video_reader.py:121-161).
     ``read_one_frame`` returns uint8 ``(y (h, w), uv (2, h/2, w/2))``, or
@@ -97,6 +117,7 @@ class YUVReader:
         else:
             self.uv_size = 2 * (height // self.sub_y) * (width // self.sub_x) * self.dtype.itemsize
         self.eof = False
+        self.skip_frame = skip_frame
         self.file = open(src_path, "rb")  # noqa: SIM115 (closed in close())
         for _ in range(skip_frame):
             if not self._read():
@@ -118,9 +139,23 @@ class YUVReader:
         r = self._read()
         if r is None:
             return None, None
-        y = np.frombuffer(r[0], dtype=self.dtype).reshape(self.height, self.width)
-        uv = np.frombuffer(r[1], dtype=self.dtype).reshape(2, self.height // self.sub_y, self.width // self.sub_x)
-        return y, uv
+        return self._planes(*r)
+
+    def _planes(self, y, uv):
+        return (np.frombuffer(y, dtype=self.dtype).reshape(self.height, self.width),
+                np.frombuffer(uv, dtype=self.dtype).reshape(2, self.height // self.sub_y, self.width // self.sub_x))
+
+    def read_frame(self, index, dst_format="420"):
+        """What the ``index``-th ``read_one_frame`` of a fresh reader returns
+        (frames skipped by ``skip_frame`` not counted), by one positional read
+        that leaves the sequential cursor alone."""
+        if dst_format not in ("420", "rgb"):
+            raise ValueError(f"unknown dst_format {dst_format!r}")
+        size = self.y_size + self.uv_size
+        data = _pread(self.file, size, (self.skip_frame + _frame_index(index)) * size)
+        if len(data) < size:
+            return None, None
+        return self._planes(data[:self.y_size], data[self.y_size:])
 
     def close(self):
         self.file.close()
@@ -156,6 +191,16 @@ class RGBReader:
             return None
         return np.frombuffer(rgb, dtype=self.dtype).reshape(3, self.height, self.width)
 
+    def read_frame(self, index, dst_format="rgb"):
+        """What the ``index``-th ``read_one_frame`` of a fresh reader returns,
+        by one positional read that leaves the sequential cursor alone."""
+        if dst_format not in ("rgb", "420"):
+            raise ValueError(f"unknown dst_format {dst_format!r}")
+        rgb = _pread(self.file, self.rgb_size, _frame_index(index) * self.rgb_size)
+        if len(rgb) < self.rgb_size:
+            return None
+        return np.frombuffer(rgb, dtype=self.dtype).reshape(3, self.height, self.width)
+
     def close(self):
         self.file.close()
 
@@ -174,24 +219,39 @@ class PNGReader:
         else:
             raise ValueError("unknown image naming convention; please specify")
         self.src_path, self.width, self.height = src_path, width, height
-        self.current_frame_index = start_num
+        self.start_num = self.current_frame_index = start_num
         self.eof = False
 
-    def read_one_frame(self, dst_format="rgb"):
+    def _load(self, number):
+        """im<number>.png as uint8 CHW RGB, or None when there is no such file."""
         from PIL import Image
-        if dst_format not in ("rgb", "420"):
-            raise ValueError(f"unknown dst_format {dst_format!r}")
-        if self.eof:
-            return None
-        p = os.path.join(self.src_path, f"im{str(self.current_frame_index).zfill(self.padding)}.png")
+        p = os.path.join(self.src_path, f"im{str(number).zfill(self.padding)}.png")
         if not os.path.exists(p):
-            self.eof = True
             return None
         rgb = np.asarray(Image.open(p).convert("RGB")).transpose(2, 0, 1)
         if rgb.shape[1:] != (self.height, self.width):
             raise ValueError(f"{p}: {rgb.shape[1:]} != {(self.height, self.width)}")
-        self.current_frame_index += 1
         return np.ascontiguousarray(rgb)
+
+    def read_one_frame(self, dst_format="rgb"):
+        if dst_format not in ("rgb", "420"):
+            raise ValueError(f"unknown dst_format {dst_format!r}")
+        if self.eof:
+            return None
+        rgb = self._load(self.current_frame_index)
+        if rgb is None:
+            self.eof = True
+            return None
+        self.current_frame_index += 1
+        return rgb
+
+    def read_frame(self, index, dst_format="rgb"):
+        """What the ``index``-th ``read_one_frame`` of a fresh reader returns
+        of a folder numbered without gaps: the file ``start_num + index``, or
+        None when there is none.  The sequential cursor stays where it is."""
+        if dst_format not in ("rgb", "420"):
+            raise ValueError(f"unknown dst_format {dst_format!r}")
+        return self._load(self.start_num + _frame_index(index))
 
     def close(self):
         self.current_frame_index = 1
@@ -212,6 +272,13 @@ class ArrayReader:
         f = self.frames[self.i]
         self.i += 1
         return f
+
+    def read_frame(self, index, dst_format="rgb"):
+        """Frame ``index`` (what the ``index``-th ``read_one_frame`` returns);
+        no state, so one reader can serve several threads."""
+        if _frame_index(index) >= len(self.frames):
+            return (None, None) if dst_format == "420" else None
+        return self.frames[index]
 
     def close(self):
         pass

@@ -16,6 +16,8 @@ drifting through the GOP.
 ``python -m dcvc_amd.sequence encode|decode ...`` wraps
 ``harness.encode_video`` / ``decode_video``.
 """
+import collections
+import os
 import struct
 
 import torch
@@ -30,6 +32,10 @@ _RECORD = struct.Struct("<BBHIQQ")          # type, flags, reserved, payload len
 _COUNT_AT = _HEADER.size - 4
 # seeds of the frame digest, by DPB entry (an I frame: x_hat under seed 1)
 DIGEST_SEEDS = (("ref_frame", 1), ("ref_feature", 2), ("ref_mv_feature", 3), ("ref_y", 4), ("ref_mv_y", 5))
+
+
+# one frame of SequenceReader.index(): where its payload lies in the file
+IndexEntry = collections.namedtuple("IndexEntry", "frame_idx type flags offset length")
 
 
 class SequenceFormatError(ValueError):
@@ -96,7 +102,8 @@ class SequenceWriter:
 class SequenceReader:
     """Header fields as attributes (codec, format, precision, bit_depth (the
     source's, 8 for a field of 0), width, height, frames); iterating yields
-    {"type", "twin", "digest" (or None), "payload"}."""
+    {"type", "twin", "digest" (or None), "payload"}.  ``index()`` and
+    ``records_from()`` give random access by frame."""
 
     def __init__(self, path):
         self.path = path
@@ -119,8 +126,45 @@ class SequenceReader:
             self.close()
             raise SequenceFormatError(f"{path}: the file was not closed by its encoder (no frame count)")
 
+    def index(self):
+        """One ``IndexEntry`` per frame, from a walk over the 24-byte record
+        headers that seeks over every payload and reads none.  The file stores
+        no index; this rebuilds it.  The sequential cursor is left where it
+        was."""
+        size = os.fstat(self.file.fileno()).st_size
+        keep = self.file.tell()
+        entries, pos = [], _HEADER.size
+        try:
+            for i in range(self.frames):
+                self.file.seek(pos)
+                head = self.file.read(_RECORD.size)
+                if len(head) < _RECORD.size:
+                    raise SequenceFormatError(f"{self.path}: truncated in the record header of frame {i}")
+                ftype, flags, _, n, _, _ = _RECORD.unpack(head)
+                if ftype > 1:
+                    raise SequenceFormatError(f"{self.path}: frame {i} has unknown type {ftype}")
+                pos += _RECORD.size
+                if pos + n > size:
+                    raise SequenceFormatError(f"{self.path}: truncated in the payload of frame {i} "
+                                              f"({max(size - pos, 0)} of {n} bytes)")
+                entries.append(IndexEntry(i, "IP"[ftype], flags, pos, n))
+                pos += n
+        finally:
+            self.file.seek(keep)
+        return entries
+
+    def records_from(self, entry, count=None):
+        """The records from ``entry`` (one of ``index()``) on, ``count`` of
+        them or up to the end of the file, as iterating yields them."""
+        self.file.seek(entry.offset - _RECORD.size)
+        stop = self.frames if count is None else min(self.frames, entry.frame_idx + count)
+        return self._records(entry.frame_idx, stop)
+
     def __iter__(self):
-        for i in range(self.frames):
+        return self._records(0, self.frames)
+
+    def _records(self, first, stop):
+        for i in range(first, stop):
             head = self.file.read(_RECORD.size)
             if len(head) < _RECORD.size:
                 raise SequenceFormatError(f"{self.path}: truncated in the record header of frame {i}")
