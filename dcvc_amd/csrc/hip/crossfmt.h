@@ -1,7 +1,7 @@
-// Colour and chroma-resampling arithmetic shared by the cross-format frame
-// kernels (crossfmt.hip: uint8 sources; frame16.hip: fp32 planes of 9..16-bit
-// sources and the uint16 writers): BT.709 in numpy's operation order, the 2x2
-// block mean, scipy's order-1 zoom taps, and the launch helpers.
+// Colour and chroma-resampling arithmetic shared by the frame kernels that
+// convert between YCbCr and RGB or resample chroma (chroma.hip, crossfmt.hip):
+// BT.709 in numpy's operation order, the 2x2 block mean, scipy's order-1 zoom
+// taps, and the launch helpers.
 //
 // Every value is bit-equal to the reference's numpy / scipy result
 // (DCVC-DC/src/transforms/functional.py:16-58), so the arithmetic is written
@@ -11,11 +11,6 @@
 #include "frame.h"
 
 namespace {
-
-// a source sample as the reader's float: uint8 / 255, or an fp32 plane value
-// that is one already (dcvc_u16_to_f32 of a 9..16-bit source)
-__device__ __forceinline__ float smp(uint8_t v) { return u8f(v); }
-__device__ __forceinline__ float smp(float v) { return v; }
 
 // ITU-R BT.709 (functional.py:10-13).  numpy multiplies float32 arrays by
 // these Python doubles as float32 scalars: each constant is the double
@@ -54,7 +49,7 @@ __device__ __forceinline__ void rgb_to_ycc(float r, float g, float b, float &y, 
 }
 
 // float32 mean of a 2x2 block as numpy's mean(axis=(-1, -3)) forms it:
-// (x00 + x01) + (x10 + x11) (sse_yuv420_kernel, frame.hip), except for a
+// (x00 + x01) + (x10 + x11), except for a
 // chroma plane one column wide (seq), whose four values numpy reduces as one
 // contiguous run, ((x00 + x01) + x10) + x11
 __device__ __forceinline__ float mean4(float x00, float x01, float x10, float x11, bool seq) {
@@ -120,7 +115,5 @@ inline unsigned cf_blocks(int64_t n) {
   const int64_t g = (n + CF_BLOCK - 1) / CF_BLOCK;
   return (unsigned)(g < CF_MAX_BLOCKS ? (g > 0 ? g : 1) : CF_MAX_BLOCKS);
 }
-
-inline bool even_frame(int h, int w) { return h >= 2 && w >= 2 && !(h & 1) && !(w & 1); }
 
 }  // namespace

@@ -1,21 +1,55 @@
 // Helpers shared by the harness-side frame kernels (frame.hip, crossfmt.hip,
-// frame16.hip, chroma.hip): the NHWC frame view, the uint8 / uint16 -> [0, 1]
-// conversions, scipy's order-0 zoom index map, the fixed-order squared-error
-// reduction and the uint8 / uint16 quantisation of the decoded-frame writers.
+// frame16.hip, chroma.hip): the NHWC frame view, sample access (a uint8 /
+// uint16 / fp32 source sample as the reader's float, a value as the writer's
+// uint8 / uint16 sample), scipy's order-0 zoom index map, the fixed-order
+// squared-error reduction, the argument predicates of the entry points, and
+// the one host launcher each operation has.
 #pragma once
 #include "common.h"
-
-namespace {
 
 struct FView {
   float *p;
   int H, W, cs, co;
 };
 
+// The sample type of a source or an output file: uint8, little-endian uint16
+// of 9..16 bits (mx = max_val(depth)), or fp32 planes already in [0, 1].
+enum FSample { FS_U8, FS_U16, FS_F32 };
+
+// One host launcher per operation; every extern "C" entry point of the four
+// files is its argument check and a call to one of these.  Each is defined
+// once, next to its kernel template (the kernels are file-local: a template
+// instantiated from two files would be compiled twice).  (sub_x, sub_y) is the
+// chroma layout, (1, 1) | (2, 1) | (2, 2); fp32 sources exist at (2, 2) only.
+// chroma.hip:
+int dcvc_internal_yuv_ingest(FSample s, float mx, int sub_x, int sub_y, const void *y, const void *uv, int h, int w,
+                             FView out, hipStream_t st);
+int dcvc_internal_yuv_ingest_rgb(FSample s, float mx, int sub_x, int sub_y, const void *y, const void *uv, int h,
+                                 int w, FView out, float *rgb_planes, hipStream_t st);
+int dcvc_internal_yuv_sse(FSample s, float mx, int sub_x, int sub_y, FView xh, const void *y, const void *uv, int h,
+                          int w, double *workspace, double *out3, hipStream_t st);
+int dcvc_internal_yuv_write(FSample s, float mx, int sub_x, int sub_y, bool from_rgb, FView xh, int h, int w,
+                            void *out, hipStream_t st);
+// frame.hip:
+int dcvc_internal_rgb_sse(FSample s, float mx, FView xh, const void *src, int h, int w, double *workspace,
+                          double *out3, hipStream_t st);
+// crossfmt.hip: uint8 HWC or uint16 planar RGB, from an RGB or a YUV 4:4:4
+// frame; the float64 MS-SSIM planes of a YUV420 (uv set) or an RGB source
+int dcvc_internal_rgb_write(FSample s, float mx, bool from_yuv, FView xh, int h, int w, void *out, hipStream_t st);
+int dcvc_internal_msssim_planes(FSample s, FView xh, const void *src, const void *uv, int h, int w, double *sp,
+                                double *rp, hipStream_t st);
+
+namespace {
+
 __device__ __forceinline__ float u8f(uint8_t v) { return (float)v / 255.f; }
 
 // a 9..16-bit sample with mx = float32((1 << depth) - 1): one IEEE division
 __device__ __forceinline__ float u16f(uint16_t v, float mx) { return (float)v / mx; }
+
+// a source sample as the reader's float; only a uint16 sample needs mx
+__device__ __forceinline__ float smp(uint8_t v, float = 0.f) { return u8f(v); }
+__device__ __forceinline__ float smp(uint16_t v, float mx) { return u16f(v, mx); }
+__device__ __forceinline__ float smp(float v, float = 0.f) { return v; }
 
 // scipy.ndimage.zoom(uv, (1, 2, 2), order=0) as ycbcr420_to_444(order=0)
 // calls it (DCVC-DC/src/transforms/functional.py:61-72): output index i of an
@@ -39,7 +73,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 // Block sum of three doubles in a fixed order: wave shuffles, then the four
 // wave results in index order.  Thread 0 writes part[3 * blockIdx.x + c].
-__device__ void block_sum3(double a0, double a1, double a2, double *part) {
+__device__ inline void block_sum3(double a0, double a1, double a2, double *part) {
   __shared__ double red[SSE_BLOCK / 64][3];
   a0 = wave_sum(a0);
   a1 = wave_sum(a1);
@@ -68,8 +102,13 @@ __device__ __forceinline__ uint16_t q16(float v, float mx) {
   return (uint16_t)fminf(fmaxf(rintf(v * mx), 0.f), mx);  // np.clip(np.rint(v * max_val), 0, max_val)
 }
 
-// Fixed-order final reduction of the per-block partials: out[c] = sum_b part[3b + c].
-__global__ void __launch_bounds__(256) sse_final_kernel(const double *part, int nb, double *out) {
+// a value as the writer's sample
+__device__ __forceinline__ void qst(uint8_t *o, float v, float) { *o = q255(v); }
+__device__ __forceinline__ void qst(uint16_t *o, float v, float mx) { *o = q16(v, mx); }
+
+// Fixed-order final reduction of the per-block partials: out[c] = sum_b part[3b + c]
+// (launched by the two distortion launchers; the other includers do not use it).
+[[maybe_unused]] __global__ void __launch_bounds__(256) sse_final_kernel(const double *part, int nb, double *out) {
   __shared__ double red[4][3];
   double a[3] = {0.0, 0.0, 0.0};
   for (int b = threadIdx.x; b < nb; b += 256)
@@ -99,6 +138,21 @@ inline bool view_ok(const float *p, int H, int W, int cs, int co) {
 }
 
 inline FView fvs(const float *p, int H, int W, int cs, int co) { return FView{const_cast<float *>(p), H, W, cs, co}; }
+
+inline bool even_frame(int h, int w) { return h >= 2 && w >= 2 && !(h & 1) && !(w & 1); }
+
+// lo = 9: the uint16-only entry points; lo = 8: those that also take uint8
+inline bool depth_ok(int depth, int lo) { return depth >= lo && depth <= 16; }
+
+inline float max_val(int depth) { return (float)((1 << depth) - 1); }
+
+// the grid of a kernel that runs one item per thread; 0: it would not fit
+constexpr int ITEM_BLOCK = 256;
+
+inline unsigned item_blocks(int64_t n) {
+  const int64_t g = (n + ITEM_BLOCK - 1) / ITEM_BLOCK;
+  return g > 0 && g <= 0x7fffffff ? (unsigned)g : 0;
+}
 
 inline unsigned sse_blocks(int64_t n) {
   const int64_t g = (n + SSE_BLOCK - 1) / SSE_BLOCK;

@@ -1,10 +1,8 @@
 // MS-SSIM of the YUV420 distortion path (calc_msssim, DCVC-DC/src/utils/
 // metrics.py:15-62, as test_video.py:182-184 calls it per plane with
-// data_range=1), in fp64 as the reference computes it.
+// data_range=1), in fp64 as the reference computes it, on the float64 planes
+// that dcvc_yuv_planes_f64 / dcvc_rgb_planes_f64 (crossfmt.hip) prepare.
 //
-//   * dcvc_yuv_planes_f64: the float64 planes calc_msssim receives: the
-//     uint8/255 source planes and the clamped recon's ycbcr444_to_420 planes
-//     (functional.py:75-95), cropped.
 //   * dcvc_ssim_level: calc_ssim's 'valid' 11x11 Gaussian filtering of img1,
 //     img2, img1^2, img2^2, img1*img2 (fftconvolve there, a direct fp64 sum
 //     here: the same linear map, rounded differently at the 1e-16 level),
@@ -22,45 +20,6 @@ constexpr int SMAXB = 1024;
 __device__ __forceinline__ double wsum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
-}
-
-struct Planes {
-  double *src;  // [Y h*w | U hh*hw | V hh*hw]
-  double *rec;
-};
-
-// one thread per 2x2 block of the crop: Y (4 pixels) and one U, V sample
-__global__ void planes_kernel(const float *xh, int xW, int xcs, int xco, const uint8_t *ysrc,
-                              const uint8_t *uvsrc, int h, int w, Planes pl) {
-  const int hh = h / 2, hw = w / 2;
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= (int64_t)hh * hw) return;
-  const int by = (int)(b / hw), bx = (int)(b - (int64_t)by * hw);
-  float v[2][2][3];
-#pragma unroll
-  for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 2; ++dx) {
-      const float *p = xh + ((int64_t)(2 * by + dy) * xW + 2 * bx + dx) * xcs + xco;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[dy][dx][c] = fminf(fmaxf(p[c], 0.f), 1.f);
-    }
-  const int64_t plane = (int64_t)h * w, cplane = (int64_t)hh * hw;
-#pragma unroll
-  for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-    for (int dx = 0; dx < 2; ++dx) {
-      const int64_t o = (int64_t)(2 * by + dy) * w + 2 * bx + dx;
-      pl.src[o] = (double)((float)ysrc[o] / 255.f);
-      pl.rec[o] = (double)v[dy][dx][0];
-    }
-#pragma unroll
-  for (int c = 1; c < 3; ++c) {
-    const float s = (v[0][0][c] + v[0][1][c]) + (v[1][0][c] + v[1][1][c]);
-    const int64_t o = plane + (int64_t)(c - 1) * cplane + b;
-    pl.src[o] = (double)((float)uvsrc[(int64_t)(c - 1) * cplane + b] / 255.f);
-    pl.rec[o] = (double)fminf(fmaxf(s / 4.f, 0.f), 1.f);
-  }
 }
 
 // calc_ssim for one level: one thread per 'valid' output pixel, 11x11 window
@@ -152,20 +111,6 @@ unsigned nblocks(int64_t n) {
 
 }  // namespace
 
-extern "C" int dcvc_yuv_planes_f64(dcvc_tensor x_hat, const uint8_t *y, const uint8_t *uv, int h, int w,
-                                   double *src_planes, double *rec_planes, void *stream) {
-  if (!x_hat.ptr || x_hat.dtype != DCVC_F32 || x_hat.C != 3 || x_hat.H < h || x_hat.W < w || !y || !uv ||
-      !src_planes || !rec_planes || h < 2 || w < 2 || (h & 1) || (w & 1))
-    return DCVC_HIP_EINVAL;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int64_t n = (int64_t)(h / 2) * (w / 2);
-  hipLaunchKernelGGL(planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                     reinterpret_cast<const float *>(x_hat.ptr), x_hat.W, x_hat.cstride, x_hat.coff, y, uv, h, w,
-                     Planes{src_planes, rec_planes});
-  DCVC_LAUNCH_CHECK();
-  return DCVC_HIP_OK;
-}
-
 extern "C" int64_t dcvc_ssim_workspace(void) { return (int64_t)2 * SMAXB * sizeof(double); }
 
 extern "C" int dcvc_ssim_level(const double *a, const double *b, int h, int w, const double *window121, double C1,
@@ -197,20 +142,6 @@ extern "C" int dcvc_down2_f64(const double *in, int h, int w, double *out, void 
 // count_include_pad=True), relu on cs / ssim).
 namespace {
 
-__global__ void rgb_planes_kernel(const float *xh, int xW, int xcs, int xco, const uint8_t *src, int h, int w,
-                                  double *sp, double *rp) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t n = (int64_t)h * w;
-  if (i >= n) return;
-  const int y = (int)(i / w), x = (int)(i - (int64_t)y * w);
-  const float *p = xh + ((int64_t)y * xW + x) * xcs + xco;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    sp[c * n + i] = (double)((float)src[c * n + i] / 255.f);
-    rp[c * n + i] = (double)fminf(fmaxf(p[c], 0.f), 1.f);
-  }
-}
-
 // F.avg_pool2d(kernel_size=2, stride=2, padding=(h % 2, w % 2)),
 // count_include_pad=True: output (h + 2 ph - 2) / 2 + 1 rows; window i covers
 // input rows 2i - ph, 2i - ph + 1 (zeros outside), always divided by 4
@@ -232,20 +163,6 @@ __global__ void avgpool2_kernel(const double *in, int h, int w, double *out) {
 }
 
 }  // namespace
-
-extern "C" int dcvc_rgb_planes_f64(dcvc_tensor x_hat, const uint8_t *src, int h, int w, double *src_planes,
-                                   double *rec_planes, void *stream) {
-  if (!x_hat.ptr || x_hat.dtype != DCVC_F32 || x_hat.C != 3 || x_hat.H < h || x_hat.W < w || !src ||
-      !src_planes || !rec_planes || h < 1 || w < 1)
-    return DCVC_HIP_EINVAL;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int64_t n = (int64_t)h * w;
-  hipLaunchKernelGGL(rgb_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                     reinterpret_cast<const float *>(x_hat.ptr), x_hat.W, x_hat.cstride, x_hat.coff, src, h, w,
-                     src_planes, rec_planes);
-  DCVC_LAUNCH_CHECK();
-  return DCVC_HIP_OK;
-}
 
 extern "C" int dcvc_avgpool2_f64(const double *in, int h, int w, double *out, void *stream) {
   if (!in || !out || h < 2 || w < 2) return DCVC_HIP_EINVAL;

@@ -873,10 +873,11 @@ SCALAR_VIEW_SYMBOLS = ("dcvc_frame16_to_nhwc", "dcvc_yuv420p16_to_nhwc", "dcvc_f
                        "dcvc_recon_to_u16_cross", "dcvc_yuv420f_to_rgb_nhwc")
 
 
-def check_depth(bit_depth):
-    """A high-bit-depth path's depth: 9..16 (8 is the uint8 code's)."""
-    if not isinstance(bit_depth, int) or not 9 <= bit_depth <= 16:
-        raise ValueError(f"bit depth {bit_depth!r} is outside 9..16")
+def check_depth(bit_depth, lo=9):
+    """A frame path's depth, lo..16: 9 for the high-bit-depth entry points (8
+    is the uint8 code's), 8 for the chroma-layout ones."""
+    if not isinstance(bit_depth, int) or isinstance(bit_depth, bool) or not lo <= bit_depth <= 16:
+        raise ValueError(f"bit depth {bit_depth!r} is outside {lo}..16")
     return bit_depth
 
 
@@ -979,9 +980,7 @@ def chroma_sub(chroma):
 
 def check_depth8(bit_depth):
     """A chroma-layout path's depth: 8..16."""
-    if not isinstance(bit_depth, int) or isinstance(bit_depth, bool) or not 8 <= bit_depth <= 16:
-        raise ValueError(f"bit depth {bit_depth!r} is outside 8..16")
-    return bit_depth
+    return check_depth(bit_depth, 8)
 
 
 def yuvp_sizes(h, w, chroma):

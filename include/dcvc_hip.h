@@ -427,8 +427,9 @@ int dcvc_rgbf_to_yuv420_planes(const float *rgb, int h, int w, float *y_plane,
  *   4:4:4: the chroma planes as they are;
  *   4:2:2: the horizontal half of the 4:2:0 arithmetic (order-0 / order-1
  *          zoom along x in, mean of each horizontal pair out);
- *   4:2:0: bit-equal to the uint8 / uint16 4:2:0 entry points above (the
- *          harness keeps routing 4:2:0 to those).
+ *   4:2:0: the kernels the uint8 / uint16 / fp32-plane 4:2:0 entry points
+ *          above run as well (the harness keeps routing 4:2:0 to those
+ *          entry points, which keep their own argument rules).
  * DCVC_HIP_EINVAL: a null pointer, a bad view, depth outside 8..16, an unknown
  * (sub_x, sub_y), odd w with sub_x = 2, odd h with sub_y = 2, a view smaller
  * than the frame.

@@ -73,7 +73,7 @@ def ingest_rgb_source_yuv_codec(rgb16, d, H, W):
 # ------------------------------------------------------------------ output
 def mean2x2_pairwise(p):
     """float32 2x2 block mean of (1, h, w), always (x00 + x01) + (x10 + x11):
-    the summation order of sse_yuv420_kernel / recon_yuv_u8_kernel."""
+    the summation order of sse_yuvp_kernel / recon_yuvp_kernel (YCbCr frame)."""
     x00, x01, x10, x11 = p[:, 0::2, 0::2], p[:, 0::2, 1::2], p[:, 1::2, 0::2], p[:, 1::2, 1::2]
     return ((x00 + x01) + (x10 + x11)) / F32(4)
 
