@@ -1030,9 +1030,23 @@ def encode_video(i_frame_net, p_frame_net, args):
     True) stores the DPB digests.  Nothing is decoded: the log's bits are the
     frames' payload bits and its PSNR is that of the ENCODER's reconstruction
     (which a decoder of the file reproduces bit for bit).  ``src_bit_depth``
-    above 8 is recorded in the file's header; the payloads do not depend on it."""
+    above 8 is recorded in the file's header; the payloads do not depend on it.
+
+    Scene-cut keyframes (off by default; there is no default threshold):
+    ``scene_cut`` / ``scene_cut_mad`` are thresholds in (0, 1] on the
+    detector's ``hd`` / ``mad`` (``scenecut.SceneCutDetector``); a frame that
+    reaches any given one (>=) is coded as an I frame once
+    ``min_keyframe_interval`` (default 1) frames have passed since the last
+    keyframe.  The log then gains "scene_cuts" (the frames coded as I because
+    of a cut) and "scene_scores" ([hd, mad] per frame, None for frame 0).  With
+    neither threshold no detector is built and the file is what it always was."""
+    from . import scenecut
     from .sequence import SequenceEncoder, codec_of
     hem = codec_of(i_frame_net) == "HEM"
+    cut_hd = scenecut.check_threshold("scene_cut", args.get("scene_cut"))
+    cut_mad = scenecut.check_threshold("scene_cut_mad", args.get("scene_cut_mad"))
+    min_interval = scenecut.check_interval(args.get("min_keyframe_interval", 1))
+    detect = cut_hd is not None or cut_mad is not None
     _tag_format((i_frame_net, p_frame_net), args)
     frame_num, gop_size = args["frame_num"], args["gop_size"]
     verbose = args.get("verbose", 0)
@@ -1055,15 +1069,28 @@ def encode_video(i_frame_net, p_frame_net, args):
                            bit_depth=src_depth)
         q = dict(q_in_ckpt=args["q_in_ckpt"], q_index=args["i_frame_q_index"])
     frame_types, bits, fallbacks = [], [], []
+    # the detector reads source samples only: one object for every codec, source type and depth
+    detector = scenecut.SceneCutDetector(h, w, src_fmt, src_depth, device) if detect else None
+    scene_cuts, scene_scores = [], []
     start_time = time.time()
     with SequenceEncoder(i_frame_net, p_frame_net, args["seq_path"], w, h, gop_size, yuv420=yuv,
-                         digest=bool(args.get("digest", True)), bit_depth=src_depth, **q) as enc:
+                         digest=bool(args.get("digest", True)), bit_depth=src_depth,
+                         min_keyframe_interval=min_interval, **q) as enc:
         for frame_idx in range(frame_num):
             frame = reader.read_one_frame(dst_format=_dst_format(src_fmt))
             if frame is None or (src_fmt != "rgb" and frame[0] is None):
                 raise ValueError(f"source ended at frame {frame_idx} of {frame_num}")
             dframe = stage.upload(frame)
-            out = enc.encode(stage.load(dframe))
+            cut = False
+            if detector is not None:
+                score = detector.score(dframe)
+                scene_scores.append(None if score is None else [score["hd"], score["mad"]])
+                cut = scenecut.is_cut(score, cut_hd, cut_mad)
+            # with no cut this is the type of frame_idx % gop_size == 0 (the schedule is not advanced here)
+            regular = enc.schedule.peek() == "I"
+            out = enc.encode(stage.load(dframe), keyframe=cut)
+            if cut and out["type"] == "I" and not regular:
+                scene_cuts.append(frame_idx)
             frame_types.append(0 if out["type"] == "I" else 1)
             bits.append(out["bit"])
             fallbacks.append(out["precision_fallback"])
@@ -1086,6 +1113,9 @@ def encode_video(i_frame_net, p_frame_net, args):
                                 [psnr_rgb(sse[i], h, w) for i in range(frame_num)], zeros, verbose=verbose >= 1)
     log["frame_bits"] = bits
     log["precision_fallbacks"] = fallbacks
+    if detect:
+        log["scene_cuts"] = scene_cuts
+        log["scene_scores"] = scene_scores
     return log
 
 
@@ -1096,7 +1126,15 @@ def decode_video(i_frame_net, p_frame_net, args):
     ``run_test_hem`` write them (``recon_path`` / ``decoded_frame_folder``;
     ``src_type`` selects PNG, out.rgb or out.yuv as there, the codec's own
     format by default; ``recon_bit_depth``, by default the source depth the
-    file's header records).  Returns the per-frame bits and types."""
+    file's header records).  Returns the per-frame bits and types.
+
+    ``start_frame`` (default 0) and ``frame_num`` (default: to the end; clipped
+    there) select the frames: decoding starts at the last keyframe at or before
+    ``start_frame`` (``SequenceDecoder.frames``) and only the selected frames
+    are returned and written, the files numbered from the first of them.  The
+    result says where: "start_frame", "keyframe", "frames_decoded", and "gops"
+    ((start, stop) of every GOP of the file, ``lanes.gops_of``)."""
+    from .lanes import gops_of
     from .sequence import SequenceDecoder, codec_of
     hem = codec_of(i_frame_net) == "HEM"
     _tag_format((i_frame_net, p_frame_net), args)
@@ -1104,6 +1142,9 @@ def decode_video(i_frame_net, p_frame_net, args):
     start_time = time.time()
     with SequenceDecoder(i_frame_net, p_frame_net, args["seq_path"]) as dec:
         h, w = dec.height, dec.width
+        start = args.get("start_frame", 0)
+        frames = dec.frames(start, args.get("frame_num"))       # a bad range raises before any folder is made
+        gops = [list(g) for g in gops_of(dec.reader.index(), dec.reader.path)]
         codec_fmt = "420" if dec.reader.format == "yuv420" else "rgb"
         src_type = args.get("src_type")
         src_fmt = _src_format(src_type, codec_fmt)
@@ -1118,10 +1159,12 @@ def decode_video(i_frame_net, p_frame_net, args):
                 writer = ReconWriter(args["recon_path"], h, w, _writer_kind(src_type, src_fmt, depth), codec_fmt,
                                      i_frame_net.dev, bit_depth=depth, chroma=_chroma(src_fmt))
         with (writer if writer is not None else contextlib.nullcontext()):
-            for frame_idx, out in enumerate(dec):
+            for emitted, out in enumerate(frames):
                 frame_types.append(0 if out["type"] == "I" else 1)
                 bits.append(out["bit"])
                 if writer is not None:
-                    writer.write(out["x_hat"], frame_idx)
+                    writer.write(out["x_hat"], emitted)
+        keyframe, decoded = dec.last_keyframe, dec.frames_decoded
     return {"frame_num": len(bits), "frame_pixel_num": h * w, "frame_type": frame_types, "frame_bits": bits,
-            "bit_depth": depth, "test_time": time.time() - start_time}
+            "bit_depth": depth, "test_time": time.time() - start_time, "start_frame": start, "keyframe": keyframe,
+            "frames_decoded": decoded, "gops": gops}

@@ -147,6 +147,8 @@ HIP_SYMBOLS = [
     ("dcvc_digest_workspace", ctypes.c_int64, []),
     ("dcvc_digest_threads", _i, []),
     ("dcvc_digest", _i, [_T, ctypes.c_uint64, _vp, _vp, _vp]),
+    ("dcvc_scene_stats_workspace", ctypes.c_int64, []),
+    ("dcvc_scene_stats", _i, [_vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp]),
     ("dcvc_debug_poison_lds", _i, [_i, _i, _vp]),
     ("dcvc_debug_poison_vgpr", _i, [_i, _vp]),
 ]
@@ -1218,3 +1220,36 @@ def digest(act, seed, out, workspace=None):
         raise NativeError("digest: unsupported dtype")
     check(status, "digest")
     return out
+
+
+# ---- scene statistics (scenecut.hip)
+def scene_stats_workspace(device):
+    """Device scratch of one dcvc_scene_stats call."""
+    return torch.empty(int(lib().dcvc_scene_stats_workspace()) // 8, dtype=torch.int64, device=device)
+
+
+def scene_stats(cur, prev, depth, workspace, out2):
+    """out2 (two device int64 words) = (sad, hdiff) of two planes of co-located
+    samples of ``depth`` bits (dcvc_scene_stats): uint8 tensors at 8, 2-byte
+    integer tensors (the bits of uint16) above; any contiguous view, at any
+    sample offset of its storage.  Raises ValueError on planes that do not
+    match the depth or each other, before anything is launched."""
+    check_depth8(depth)
+    kind = "uint8" if depth == 8 else "2-byte integer"
+    for t in (cur, prev):
+        if not isinstance(t, torch.Tensor) or t.dtype.is_floating_point or t.dtype == torch.bool or \
+                t.element_size() != (1 if depth == 8 else 2) or (depth == 8 and t.dtype != torch.uint8):
+            raise ValueError(f"a plane of {depth}-bit samples is a {kind} tensor, not {getattr(t, 'dtype', type(t))}")
+        if not t.is_contiguous():
+            raise ValueError("the planes must be contiguous")
+    if cur.dtype != prev.dtype or cur.numel() != prev.numel() or cur.numel() < 1:
+        raise ValueError(f"the planes differ or are empty: {cur.dtype} x {cur.numel()}, {prev.dtype} x {prev.numel()}")
+    if cur.device != prev.device or workspace.device != cur.device or out2.device != cur.device:
+        raise ValueError("the planes, the workspace and out2 must be on one device")
+    if out2.dtype != torch.int64 or out2.numel() < 2 or not out2.is_contiguous():
+        raise ValueError("out2 must be a contiguous int64 tensor of two words")
+    if workspace.numel() * workspace.element_size() < int(lib().dcvc_scene_stats_workspace()):
+        raise ValueError("the workspace is smaller than dcvc_scene_stats_workspace()")
+    check(lib().dcvc_scene_stats(cur.data_ptr(), prev.data_ptr(), cur.numel(), depth, workspace.data_ptr(),
+                                 out2.data_ptr(), stream()), "scene_stats")
+    return out2

@@ -6,7 +6,8 @@ An I frame resets the DPB, every payload carries its own q and ``frame_idx``
 and a frame's digest covers only that frame's DPB, so the GOPs of a sequence
 file are independent pieces of work.  This module holds what a driver that
 codes them at once needs on the host and nothing that touches a GPU:
-``gop_ranges`` / ``gops_of`` say which pieces there are, ``LanePool`` hands
+``gop_ranges`` / ``gops_of`` say which pieces there are (``keyframe_before``:
+the piece a frame lies in, where a seek starts decoding), ``LanePool`` hands
 them to lanes and keeps the order, the memory bound and the failure rules.
 The readers' ``read_frame`` (harness.py) and ``SequenceReader.index()``
 (sequence.py) give each lane random access to its frames.
@@ -34,6 +35,20 @@ def gops_of(index, path="the file"):
         raise SequenceFormatError(f"{path}: frame 0 is a P frame with no frame before it")
     starts = [e.frame_idx for e in index if e.type == "I"]
     return list(zip(starts, starts[1:] + [len(index)]))
+
+
+def keyframe_before(index, frame_idx, path="the file"):
+    """The ``IndexEntry`` of the last I frame at or before ``frame_idx`` in
+    ``SequenceReader.index()``: where a decode that wants ``frame_idx`` starts."""
+    from .sequence import SequenceFormatError
+    if isinstance(frame_idx, bool) or not isinstance(frame_idx, int) or not 0 <= frame_idx < len(index):
+        raise ValueError(f"frame {frame_idx!r} is outside 0..{len(index) - 1}")
+    if index[0].type != "I":
+        raise SequenceFormatError(f"{path}: frame 0 is a P frame with no frame before it")
+    k = frame_idx
+    while index[k].type != "I":
+        k -= 1
+    return index[k]
 
 
 class Lane:

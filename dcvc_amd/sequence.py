@@ -249,11 +249,17 @@ class SequenceEncoder:
     schedule, the P codec's q and ``frame_idx`` are those of ``run_test`` /
     ``run_test_hem``: DC passes (q_in_ckpt, q_index) to both codecs and
     ``frame_idx % 4``; HEM passes i_frame_q_scale and the two P scales.
+    ``encode(x, keyframe=True)`` asks for an I frame out of turn (a scene cut):
+    the ``scenecut.KeyframeSchedule`` grants it once ``min_keyframe_interval``
+    frames have passed since the last keyframe and counts ``gop_size`` from it
+    again.  The DC P codec keeps the global ``frame_idx % 4`` (the decoder
+    reads it from the payload).
     ``bit_depth`` is the source's, for the header only: no payload depends on it."""
 
     def __init__(self, i_net, p_net, path, width, height, gop_size, q_in_ckpt=False, q_index=None,
                  i_frame_q_scale=None, p_frame_mv_y_q_scale=None, p_frame_y_q_scale=None, yuv420=False, digest=True,
-                 bit_depth=8):
+                 bit_depth=8, min_keyframe_interval=1):
+        from .scenecut import KeyframeSchedule
         self.codec, fmt, prec = _describe(i_net, p_net)
         if fmt != FORMATS[int(bool(yuv420))]:
             raise ValueError(f"the nets carry codec_format {fmt!r}, the caller asks for {FORMATS[int(bool(yuv420))]!r}")
@@ -267,14 +273,15 @@ class SequenceEncoder:
                                                                   p_frame_y_q_scale)
         self.digest = FrameDigest(i_net.dev) if digest else None
         header_bit_depth(bit_depth)     # before the file is created
+        self.schedule = KeyframeSchedule(gop_size, min_keyframe_interval)
         self.writer = SequenceWriter(path, self.codec, fmt, prec, width, height, bit_depth=bit_depth)
         self.dpb = None
         self.n = 0
 
-    def encode(self, x):
+    def encode(self, x, keyframe=False):
         frame_idx = self.n
         with torch.no_grad():
-            if frame_idx % self.gop_size == 0:
+            if self.schedule.next(cut=bool(keyframe)) == "I":
                 if self.codec == "DC":
                     out = self.i_net.encode_frame(x, self.q[0], self.q[1], self.height, self.width)
                 else:
@@ -304,9 +311,25 @@ class SequenceEncoder:
         return False
 
 
+class _FrameCount(int):
+    """``SequenceDecoder.frames``: the file's frame count (an int, as it has
+    always been), which can also be called: ``dec.frames(start, count)`` is the
+    generator of those frames."""
+
+    def __new__(cls, n, generator):
+        self = super().__new__(cls, n)
+        self._generator = generator
+        return self
+
+    def __call__(self, start=0, count=None):
+        return self._generator(start, count)
+
+
 class SequenceDecoder:
     """Decoder only: iterating yields, per frame, {"type", "x_hat" (the
-    (1, 3, H, W) decoded frame), "dpb", "bit"}.  Raises ValueError when the
+    (1, 3, H, W) decoded frame), "dpb", "bit"}; ``frames(start, count)`` yields
+    a range of them, decoding from the last keyframe before it (``frames`` is
+    also the file's frame count).  Raises ValueError when the
     nets are not what the header says wrote the file, DigestMismatch when a
     stored digest is not the digest of this decoder's DPB, and
     SequenceFormatError on a truncated or unclosed file."""
@@ -320,12 +343,17 @@ class SequenceDecoder:
             r.close()
             raise ValueError(f"{path} was written by {theirs} codecs (codec, format, precision); these are {mine}")
         self.i_net, self.p_net, self.codec = i_net, p_net, r.codec
-        self.width, self.height, self.frames = r.width, r.height, r.frames
+        self.width, self.height, self.frames = r.width, r.height, _FrameCount(r.frames, self._frames)
         self.digest = FrameDigest(i_net.dev)
+        self.last_keyframe = self.frames_decoded = None     # set by frames()
 
     def __iter__(self):
+        return self._decode(self.reader, 0)
+
+    def _decode(self, records, first):
+        """Decode ``records`` (frame ``first`` on), verifying every stored digest."""
         dpb = None
-        for idx, rec in enumerate(self.reader):
+        for idx, rec in enumerate(records, first):
             with torch.no_grad():
                 if rec["type"] == "I":
                     x_hat = self.i_net.decode_frame(rec["payload"], None, self.height, self.width,
@@ -341,6 +369,41 @@ class SequenceDecoder:
                     if got != rec["digest"]:
                         raise DigestMismatch(idx, rec["digest"], got)
             yield {"type": rec["type"], "x_hat": dpb["ref_frame"], "dpb": dpb, "bit": len(rec["payload"]) * 8}
+
+    def seek(self, start=0, count=None):
+        """(keyframe entry, stop) of ``frames(start, count)``: the ``IndexEntry``
+        of the last I frame at or before ``start`` and the index after the last
+        frame it yields.  Reads record headers only; raises ValueError for a
+        ``start`` outside the file or a ``count`` below 1."""
+        from .lanes import keyframe_before
+        if count is not None and (isinstance(count, bool) or not isinstance(count, int) or count < 1):
+            raise ValueError(f"count {count!r} is not None or an integer >= 1")
+        key = keyframe_before(self.reader.index(), start, self.reader.path)
+        total = self.reader.frames
+        return key, total if count is None else min(total, start + count)
+
+    def _frames(self, start=0, count=None):
+        """``frames(start, count)``: the frames ``start .. start + count - 1``
+        (to the end of the file when ``count`` is None or reaches past it), as
+        a generator; ``frames`` is this, callable.  Each frame is as ``__iter__`` yields
+        it plus "frame_idx".  Decoding starts at the last keyframe at or before
+        ``start`` (``lanes.keyframe_before``) and reads no payload before it;
+        the frames between the keyframe and ``start`` are decoded, verified
+        against their stored digests like the others, and dropped.
+        ``last_keyframe`` and ``frames_decoded`` say afterwards where the call
+        started and how many frames it decoded."""
+        if self.reader.frames == 0 and start == 0 and count is None:
+            return iter(())                     # a file of no frames, read from its start
+        key, stop = self.seek(start, count)     # a bad range raises here, at the call
+        return self._range(key, start, stop)
+
+    def _range(self, key, start, stop):
+        self.last_keyframe, self.frames_decoded = key.frame_idx, 0
+        records = self.reader.records_from(key, stop - key.frame_idx)
+        for idx, out in enumerate(self._decode(records, key.frame_idx), key.frame_idx):
+            self.frames_decoded += 1
+            if idx >= start:
+                yield dict(out, frame_idx=idx)
 
     def close(self):
         self.reader.close()
@@ -391,8 +454,18 @@ def main(argv=None):
     ap.add_argument("--src_path")
     ap.add_argument("--src_width", type=int)
     ap.add_argument("--src_height", type=int)
-    ap.add_argument("--frame_num", type=int)
+    ap.add_argument("--frame_num", type=int,
+                    help="encode: frames to code; decode: frames to emit (default: to the end)")
     ap.add_argument("--gop_size", type=int, default=32)
+    ap.add_argument("--scene_cut", type=float, default=None,
+                    help="encode: code a keyframe where the histogram distance hd of the source reaches this "
+                         "threshold in (0, 1] (default: off; there is no default threshold)")
+    ap.add_argument("--scene_cut_mad", type=float, default=None,
+                    help="encode: the same on the mean absolute difference mad")
+    ap.add_argument("--min_keyframe_interval", type=int, default=1,
+                    help="encode: frames that must have passed since the last keyframe before a cut makes another")
+    ap.add_argument("--start_frame", type=int, default=0,
+                    help="decode: first frame to emit; decoding starts at the last keyframe at or before it")
     ap.add_argument("--q_in_ckpt", action="store_true")
     ap.add_argument("--q_index", type=int, default=None)
     ap.add_argument("--i_frame_q_scale", type=float, default=None)
@@ -411,9 +484,11 @@ def main(argv=None):
         args.update(src_path=a.src_path, src_width=a.src_width, src_height=a.src_height, frame_num=a.frame_num,
                     gop_size=a.gop_size, q_in_ckpt=a.q_in_ckpt, i_frame_q_index=a.q_index,
                     i_frame_q_scale=a.i_frame_q_scale, p_frame_mv_y_q_scale=a.p_frame_mv_y_q_scale,
-                    p_frame_y_q_scale=a.p_frame_y_q_scale, verbose=1)
+                    p_frame_y_q_scale=a.p_frame_y_q_scale, verbose=1, scene_cut=a.scene_cut,
+                    scene_cut_mad=a.scene_cut_mad, min_keyframe_interval=a.min_keyframe_interval)
         out = harness.encode_video(i_net, p_net, args)
     else:
+        args.update(start_frame=a.start_frame, frame_num=a.frame_num)
         if a.recon_path is not None:
             args.update(save_decoded_frame=True, recon_path=a.recon_path, decoded_frame_folder=a.recon_path)
         out = harness.decode_video(i_net, p_net, args)

@@ -627,6 +627,26 @@ int dcvc_digest_threads(void);
 int dcvc_digest(dcvc_tensor t, uint64_t seed, uint64_t *workspace,
                 uint64_t *out, void *stream);
 
+/*
+ * Scene statistics of two planes of n co-located samples (scenecut.hip), what
+ * the encoder's scene-cut detector reads per frame.  depth = 8: uint8 samples;
+ * 9..16: native (little-endian) uint16, read unsigned.  The planes may start
+ * at any sample (no 16-byte alignment is assumed).
+ *   out2[0] = sad   = sum_i |cur[i] - prev[i]|
+ *   out2[1] = hdiff = sum_b |hist_cur[b] - hist_prev[b]| over 64 bins, the bin
+ *             of a sample being min(sample >> (depth - 6), 63) (only a sample
+ *             above (1 << depth) - 1 meets the min)
+ * Both are exact integers, equal to a host restatement whatever the reduction
+ * order.  No global atomics; every call writes both words of out2 and every
+ * workspace element it reads.  workspace: dcvc_scene_stats_workspace() bytes
+ * of device scratch, 8-byte aligned like out2.
+ * DCVC_HIP_EINVAL: a null or misaligned pointer, n < 1 or n >= 2^31, depth
+ * outside 8..16.
+ */
+int64_t dcvc_scene_stats_workspace(void);
+int dcvc_scene_stats(const void *cur, const void *prev, int64_t n, int depth,
+                     void *workspace, int64_t *out2, void *stream);
+
 /* Debug aid: fill the LDS of `blocks` workgroups with all-ones bytes (NaN in
  * bf16 / fp32), to expose kernels that read LDS they never wrote
  * (scripts/lds_poison_check.py).  Not used by the codec. */

@@ -62,6 +62,53 @@ def time_kernels(a, K, torch, dev, sync):
             "copy_read_plus_write_GBps": round(2 * nbytes / (statistics.median(cpy) * 1e-6) / 1e9, 1)}
 
 
+def time_scene_cut(a, K, torch, dev, sync, nets):
+    """What the scene-cut detector costs: whole-call encode_video time per
+    frame over ``--scene-frames`` frames with scene_cut set to a value that
+    never fires on this source (1.0: disjoint histograms) against the same call
+    without it, alternating, ``--repeats`` pairs after one warm-up pair; and
+    dcvc_scene_stats alone on one plane (device events)."""
+    from dcvc_amd.harness import ArrayReader, encode_video
+    from dcvc_amd.synth import moving_pattern
+    h, w, n = a.height, a.width, a.scene_frames
+    frames = [moving_pattern(h, w, t, seed=1) for t in range(n)]
+    base = {"frame_num": n, "gop_size": a.gop, "src_height": h, "src_width": w, "q_in_ckpt": False,
+            "i_frame_q_index": a.q_index}
+    off, on, cuts = [], [], 0
+    with tempfile.TemporaryDirectory() as td:
+        def once(**more):
+            sync()
+            t0 = time.perf_counter()
+            log = encode_video(*nets, dict(base, src_reader=ArrayReader(frames), seq_path=os.path.join(td, "s.seq"),
+                                           **more))
+            sync()
+            return 1e3 * (time.perf_counter() - t0) / n, log
+        once(frame_num=min(n, a.warmup_frames))
+        once(frame_num=min(n, a.warmup_frames), scene_cut=1.0)
+        for _ in range(a.repeats):
+            off.append(once()[0])
+            ms, log = once(scene_cut=1.0)
+            on.append(ms)
+            cuts += len(log["scene_cuts"])
+    cur, prev = (torch.from_numpy(f).to(dev)[1] for f in frames[:2])
+    ws, out = K.scene_stats_workspace(dev), torch.empty(2, dtype=torch.int64, device=dev)
+    for _ in range(5):
+        K.scene_stats(cur, prev, 8, ws, out)
+    sync()
+    runs = []
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.kernel_iters):
+            K.scene_stats(cur, prev, 8, ws, out)
+        e1.record()
+        e1.synchronize()
+        runs.append(1e3 * e0.elapsed_time(e1) / a.kernel_iters)
+    return {"scene_cut": {"frames": n, "ms_per_frame_off": [round(v, 3) for v in off],
+                          "ms_per_frame_on": [round(v, 3) for v in on], "cuts_fired": cuts,
+                          "scene_stats_us": summary(runs), "plane_samples": h * w}}
+
+
 def summary(v):
     return {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
 
@@ -78,7 +125,9 @@ def main():
     ap.add_argument("--kernel-iters", type=int, default=50)
     ap.add_argument("--paths", default="encode_only,decode_only,encode_decode,kernels",
                     help="comma list of what to time (encode_decode alone also runs on a tree without the "
-                         "stand-alone pair, for a comparison with an earlier commit)")
+                         "stand-alone pair, for a comparison with an earlier commit; scene_cut: encode_video "
+                         "with and without the scene-cut detector)")
+    ap.add_argument("--scene-frames", type=int, default=64, help="frames per encode_video call of the scene_cut path")
     a = ap.parse_args()
     paths = set(a.paths.split(","))
     pair = bool(paths & {"encode_only", "decode_only"})
@@ -111,7 +160,9 @@ def main():
     dev = enc_nets[0].dev
     h, w, n = a.height, a.width, a.gop
     stage = FrameStage(h, w, 16, False, zero_pad=False, frame_num=n, device=dev)
-    xs = [stage.load(stage.upload(moving_pattern(h, w, t, seed=1))).nchw_view().clone() for t in range(n)]
+    coded = bool(paths & {"encode_only", "decode_only", "encode_decode"})
+    xs = [stage.load(stage.upload(moving_pattern(h, w, t, seed=1))).nchw_view().clone()
+          for t in range(n if coded else 0)]
     sync = torch.cuda.current_stream(dev).synchronize
 
     def run_encode(path, frames):
@@ -191,6 +242,8 @@ def main():
     kernels = {}
     if "kernels" in paths:
         kernels = time_kernels(a, K, torch, dev, sync)
+    if "scene_cut" in paths:
+        kernels.update(time_scene_cut(a, K, torch, dev, sync, enc_nets))
 
     print(json.dumps({
         "what": "sequence_bench", "device": torch.cuda.get_device_name(dev), "height": h, "width": w, "gop": a.gop,
